@@ -12,12 +12,24 @@ tile-pairs are independent; hash-sharded; xGMI idle by design).
 torch.distributed is used ONLY for the barrier and the max-over-ranks
 timing reduction (control plane).
 
-Emits ONE JSON line from rank 0 with the driver contract fields plus
+A plain run does only what the headline figure needs: synthesize the
+resident inputs, warm up, time --steps steps, check the last step's shifts
+against the synthesis ground truth (free: the results are already on the
+host), optionally --dump-outputs, and emit ONE JSON line from rank 0 with
+the driver contract fields (metric, value, unit, ms_per_step, ...).
+
+--full adds to that line everything else the benchmark reports:
   roofline     — dominant kernel, achieved algorithmic GB/s vs 8 TB/s HBM
                  peak (HIP-event timed inside this run; see DESIGN.md for
                  the per-kernel algorithmic-byte formulas),
-  cpu_baseline — the oracle (CPU restatement, kind "port") timed on this
-                 box's host cores on a bounded sample of the same workload.
+  kernel_ms_per_pair — per-kernel HIP-event time per pair,
+  cpu_baseline — the oracle (CPU restatement, kind "port") timed on the
+                 host cores on a bounded sample of the same workload
+                 (skipped with --no-cpu-baseline).
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(shift, r, valid per pair) as DIR/<name>.npy, float64. Inputs are seeded,
+so two builds run with the same arguments can be compared array by array.
 """
 
 import argparse
@@ -131,6 +143,22 @@ def cpu_baseline_leg(ctx, size, cores, ds=(1, 1, 1)):
     }
 
 
+def dump_outputs(outdir, res, rank, world):
+    """Write the last timed step's stitch_batch results (what a caller of
+    the timed path receives) as float64 .npy files: shift (pairs, 3) in
+    (x, y, z) px, r (pairs,), valid (pairs,) as 0/1. One set per rank at
+    N>1 (each rank stitches its own pair set)."""
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    arrays = {
+        "shift": np.array([r["shift"] for r in res], np.float64),
+        "r": np.array([r["r"] for r in res], np.float64),
+        "valid": np.array([r["valid"] for r in res], np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,7 +169,15 @@ def main():
     ap.add_argument("--distinct", type=int, default=8,
                     help="distinct synthesized pairs per GPU")
     ap.add_argument("--overlap", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report roofline, per-kernel times and the "
+                         "CPU baseline (a plain run reports the headline "
+                         "figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as "
+                         "DIR/<name>.npy (float64)")
     ap.add_argument("--pad-mode", default="pow2", choices=["pow2", "fast"],
                     help="[PIN-PAD] FFT pad rule (fast = even 7-smooth)")
     ap.add_argument("--ds", default="1,1,1",
@@ -149,6 +185,8 @@ def main():
                          "2,2,1; the HEADLINE workload uses 1,1,1 = more "
                          "work per pair). Adds k_downsample to the path.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -224,11 +262,67 @@ def main():
     errcap = max(1.0, 0.75 * max(dsv))  # subpixel precision is ds-scaled
     assert err < errcap, f"bench shifts off ground truth by {err}"
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
+
     total_pairs = args.steps * args.pairs * world
     value = total_pairs / elapsed
 
-    stats = ctx.stats()
-    ab = algorithmic_bytes_per_launch(args.size, dsv)
+    # everything past the headline figure is --full only
+    extra = {}
+    if args.full:
+        stats = ctx.stats()
+        extra["roofline"] = roofline_leg(stats, args.size, dsv, value)
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cores = os.cpu_count() or 1
+            cpu = cpu_baseline_leg(ctx, args.size, cores, ds=dsv)
+            cpu["value"] = round(cpu["value"], 4)
+        extra["cpu_baseline"] = cpu
+        extra["kernel_ms_per_pair"] = {
+            kname: round(k["total_ms"] / max(1, stats["pairs"]), 4)
+            for kname, k in stats["kernels"].items()
+            if k["launches"] > 0
+        }
+
+    if rank == 0:
+        line = {
+            "metric": "tile-pairs/sec phase-correlated (512^3 uint16)",
+            "value": round(value, 3),
+            "unit": "tile-pairs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,  # reference publishes no numbers (BASELINE.md)
+            "dtype": "f32+i64",
+            "data": "synthetic",
+            "config": {
+                "workload": (
+                    f"BASELINE.json configs[1]: {args.pairs}x{args.size}^3 "
+                    f"uint16 tile-pairs per GPU, ~{int(args.overlap*100)}% "
+                    f"x-overlap content, ds={args.ds}, peaks=5, subpixel, "
+                    f"{n_distinct} distinct scenes, no collectives"
+                ),
+                "pairs_per_gpu": args.pairs,
+                "tile": f"{args.size}^3",
+                "parallelism": f"dp{world} hash-sharded pairs",
+            },
+            **extra,
+            "max_abs_shift_err_px": round(float(err), 4),
+        }
+        print(json.dumps(line))
+    ctx.close()
+    if dist:
+        dist.destroy_process_group()
+
+
+def roofline_leg(stats, size, dsv, value):
+    """Dominant-kernel and whole-path algorithmic GB/s vs the HBM peak,
+    from the HIP-event stats of the timed steps (value = pairs/s)."""
+    ab = algorithmic_bytes_per_launch(size, dsv)
     dom, dom_ms = None, -1.0
     for kname, b in ab.items():
         k = stats["kernels"][kname]
@@ -240,7 +334,7 @@ def main():
         avg_ms = k["total_ms"] / k["launches"]
         achieved = ab[dom] / (avg_ms * 1e-3) / 1e9  # GB/s
         traffic = None
-        sidecar = (load_traffic_sidecar(args.size)
+        sidecar = (load_traffic_sidecar(size)
                    if dsv == (1, 1, 1) else None)  # sidecar is ds=1 PMC
         if sidecar and dom in sidecar.get("kernels", {}):
             traffic = sidecar["kernels"][dom]
@@ -268,53 +362,7 @@ def main():
             "aggregate_achieved": round(agg, 1),
             "aggregate_frac": round(agg / HBM_PEAK_GBS, 4),
         }
-
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cores = os.cpu_count() or 1
-        cpu = cpu_baseline_leg(ctx, args.size, cores, ds=dsv)
-        cpu["value"] = round(cpu["value"], 4)
-
-    if rank == 0:
-        line = {
-            "metric": "tile-pairs/sec phase-correlated (512^3 uint16)",
-            "value": round(value, 3),
-            "unit": "tile-pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,  # reference publishes no numbers (BASELINE.md)
-            "dtype": "f32+i64",
-            "data": "synthetic",
-            "config": {
-                "workload": (
-                    f"BASELINE.json configs[1]: {args.pairs}x{args.size}^3 "
-                    f"uint16 tile-pairs per GPU, ~{int(args.overlap*100)}% "
-                    f"x-overlap content, ds={args.ds}, peaks=5, subpixel, "
-                    f"{n_distinct} distinct scenes, no collectives"
-                ),
-                "pairs_per_gpu": args.pairs,
-                "tile": f"{args.size}^3",
-                "parallelism": f"dp{world} hash-sharded pairs",
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "kernel_ms_per_pair": {
-                kname: round(
-                    stats["kernels"][kname]["total_ms"]
-                    / max(1, stats["pairs"]), 4)
-                for kname in stats["kernels"]
-                if stats["kernels"][kname]["launches"] > 0
-            },
-            "max_abs_shift_err_px": round(float(err), 4),
-        }
-        print(json.dumps(line))
-    ctx.close()
-    if dist:
-        dist.destroy_process_group()
+    return roofline
 
 
 if __name__ == "__main__":

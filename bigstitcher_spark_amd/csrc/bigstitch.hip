@@ -2069,9 +2069,14 @@ __device__ __forceinline__ u64 splitmix64(u64 x) {
 }
 
 /* blobs: packed {cx,cy,cz,sigma,amp} per blob; one workgroup per blob,
- * atomicAdd into the float accumulator over the 3-sigma support. */
+ * atomicAdd into the accumulator over the 3-sigma support. The
+ * accumulator is 64-bit fixed point (2^-20 counts): integer adds commute,
+ * so the rendered tile is bit-identical from run to run whatever order
+ * the workgroups arrive in (a float atomic sum is not). Negative
+ * contributions wrap in two's complement and sum correctly. */
+#define BS_SYNTH_FIX 1048576.0f /* 2^20 */
 __global__ __launch_bounds__(256) void k_synth_blobs(
-    float *acc, int nx, int ny, int nz, const float *blobs) {
+    unsigned long long *acc, int nx, int ny, int nz, const float *blobs) {
   const float *b = blobs + (long)blockIdx.x * 5;
   float cx = b[0], cy = b[1], cz = b[2], sg = b[3], am = b[4];
   float r = 3.0f * sg;
@@ -2089,17 +2094,19 @@ __global__ __launch_bounds__(256) void k_synth_blobs(
     float fx = (float)(x0 + x) - cx, fy = (float)(y0 + y) - cy,
           fz = (float)(z0 + z) - cz;
     float v = am * __expf((fx * fx + fy * fy + fz * fz) * inv2s2);
-    atomicAdd(&acc[((long)(z0 + z) * ny + y0 + y) * nx + x0 + x], v);
+    atomicAdd(&acc[((long)(z0 + z) * ny + y0 + y) * nx + x0 + x],
+              (unsigned long long)__float2ll_rn(v * BS_SYNTH_FIX));
   }
 }
 
 __global__ __launch_bounds__(256) void k_synth_quant(
-    const float *acc, unsigned short *out, long n, u64 seed,
+    const unsigned long long *acc, unsigned short *out, long n, u64 seed,
     unsigned short floorv, unsigned short amp) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long)gridDim.x * blockDim.x) {
     float noise = (float)(splitmix64(seed ^ (u64)i) % (u64)amp);
-    float v = acc[i] + (float)floorv + noise;
+    float sum = (float)((double)(long long)acc[i] * (1.0 / BS_SYNTH_FIX));
+    float v = sum + (float)floorv + noise;
     v = fminf(fmaxf(rintf(v), 0.0f), 65535.0f);
     out[i] = (unsigned short)v;
   }
@@ -2234,7 +2241,7 @@ struct bs_ctx {
   std::map<int32_t, bs_view_rec> views;
   std::map<int, f2 *> twiddles;
   bs_slot slot[BS_NSLOTS];
-  float *synth_acc = nullptr;
+  unsigned long long *synth_acc = nullptr; /* fixed-point, see k_synth_blobs */
   size_t synth_cap = 0;
   void *fuse_out = nullptr;
   size_t fuse_cap = 0;
@@ -2563,7 +2570,7 @@ extern "C" int bs_view_synth(bs_ctx *c, int32_t id, const int64_t dims[3],
   CHK(c, hipSetDevice(c->dev));
   long nx = dims[0], ny = dims[1], nz = dims[2];
   size_t n = (size_t)nx * ny * nz;
-  int rc = ensure_dev(c, (void **)&c->synth_acc, &c->synth_cap, n * 4);
+  int rc = ensure_dev(c, (void **)&c->synth_acc, &c->synth_cap, n * 8);
   if (rc) return rc;
   rc = ensure_dev(c, (void **)&c->dblobs, &c->dblobs_cap,
                   (size_t)std::max(1, n_blobs) * 5 * 4);
@@ -2576,7 +2583,7 @@ extern "C" int bs_view_synth(bs_ctx *c, int32_t id, const int64_t dims[3],
   }
   unsigned short *d;
   CHK(c, hipMalloc(&d, n * 2));
-  CHK(c, hipMemsetAsync(c->synth_acc, 0, n * 4, c->stream));
+  CHK(c, hipMemsetAsync(c->synth_acc, 0, n * 8, c->stream));
   if (n_blobs > 0) {
     CHK(c, hipMemcpyAsync(c->dblobs, blobs, (size_t)n_blobs * 5 * 4,
                           hipMemcpyHostToDevice, c->stream));

@@ -78,7 +78,9 @@ int bs_view_release(bs_ctx *ctx, int32_t view_id);
 /* Device-generated synthetic view (bench path only; BASELINE.json §(d)):
  * seeded Gaussian-blob content + noise floor. blob array is packed
  * {cx,cy,cz,sigma,amplitude} float5 per blob, positions in THIS view's
- * local coordinates (may lie outside [0,dims)). */
+ * local coordinates (may lie outside [0,dims)). Overlapping blobs are
+ * summed in fixed point, so the same arguments give a bit-identical view
+ * on every call. */
 int bs_view_synth(bs_ctx *ctx, int32_t view_id, const int64_t dims[3],
                   const float *blobs, int32_t n_blobs, uint32_t noise_seed,
                   uint16_t noise_floor, uint16_t noise_amp);
