@@ -65,7 +65,7 @@ class _FuseParams(C.Structure):
 BS_K_NAMES = [
     "downsample", "fft_x_fwd", "fft_y_fwd", "fft_z_fwd", "fft_z_inv",
     "fft_y_inv", "fft_x_inv", "peak", "peak_merge", "corr", "subpix",
-    "fuse", "synth", "pyramid",
+    "fuse", "synth", "pyramid", "peak_rows",
 ]
 _NK = len(BS_K_NAMES)
 
@@ -133,6 +133,11 @@ def load_lib():
                                    C.POINTER(C.c_void_p)]
     lib.bs_get_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
     lib.bs_reset_stats.argtypes = [C.c_void_p]
+    lib.bs_debug_last_top5.argtypes = [C.c_void_p, C.c_float * 5,
+                                       C.c_int64 * 5]
+    lib.bs_debug_peak_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3,
+                                       C.c_int, C.c_float * 5, C.c_int64 * 5,
+                                       C.POINTER(C.c_int)]
     _lib = lib
     return lib
 
@@ -349,6 +354,32 @@ class Context:
             "bs_fuse_volume",
         )
         return outs
+
+    # -- debug (not part of the product surface) --------------------------
+    def debug_last_top5(self):
+        """Top five PCM maxima of the last stitched pair as the candidate
+        stage received them: (values float32[5], linear indices int64[5])."""
+        v, idx = (C.c_float * 5)(), (C.c_int64 * 5)()
+        self._check(self._lib.bs_debug_last_top5(self._h, v, idx),
+                    "bs_debug_last_top5")
+        return np.array(v[:], np.float32), np.array(idx[:], np.int64)
+
+    def debug_peak_scan(self, vol: np.ndarray, mode: str = "auto"):
+        """Run the stitch path's peak stage on a (pz, py, px) float32
+        volume. Returns (values float32[5], indices int64[5], fell_back)."""
+        vol = np.ascontiguousarray(vol, np.float32)
+        pz, py, px = vol.shape
+        v, idx = (C.c_float * 5)(), (C.c_int64 * 5)()
+        fb = C.c_int(0)
+        self._check(
+            self._lib.bs_debug_peak_scan(
+                self._h, vol.ctypes.data_as(C.c_void_p),
+                (C.c_int64 * 3)(px, py, pz), {"auto": 0, "full": 1}[mode],
+                v, idx, C.byref(fb)),
+            "bs_debug_peak_scan",
+        )
+        return (np.array(v[:], np.float32), np.array(idx[:], np.int64),
+                bool(fb.value))
 
     # -- stats ------------------------------------------------------------
     def stats(self):

@@ -893,6 +893,15 @@ __global__ __launch_bounds__(LPB_S *TPL_S) __attribute__((amdgpu_waves_per_eu(8)
                                   twg);
 }
 
+/* max over a wave's lanes, result in every lane (the inverse x kernels
+ * hold one PCM row per wave: this is the row maximum the peak prefilter
+ * works from; fmaxf like the scan, so NaNs are ignored the same way) */
+__device__ __forceinline__ float wave_max_f32(float m) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  return m;
+}
+
 /* Inverse x pass (C2R, packed): per-line Hermitian half-line -> the real
  * PCM line via an (n/2)-point inverse complex FFT. Build
  * Z2[k] = A + i*conj(W^k)*B with A = X[k]+conj(X[h-k]),
@@ -900,8 +909,8 @@ __global__ __launch_bounds__(LPB_S *TPL_S) __attribute__((amdgpu_waves_per_eu(8)
  * UNNORMALIZED length-n inverse, matching the other passes); after the
  * FFT, z[j] = (pcm[2j], pcm[2j+1]) -> vectorized float2 row writes. */
 __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv(
-    const f2 *in, float *out, int n, int log2n, int cx, long cxp,
-    long nlines, const f2 *twg) {
+    const f2 *in, float *out, float *rowmax, int n, int log2n, int cx,
+    long cxp, long nlines, const f2 *twg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = n >> 1, log2h = log2n - 1;
   f2 *tw = (f2 *)smem;
@@ -934,7 +943,14 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv(
     fft_lds<1, TPL_X>(data, (long)line * h, h, log2h, tl, tw, -1);
     if (active) {
       f2 *o = (f2 *)(out + lid * n); /* rows are 8B-aligned (n >= 4) */
-      for (int j = tl; j < h; j += TPL_X) o[j] = ld[j];
+      float m = -3.0e38f;
+      for (int j = tl; j < h; j += TPL_X) {
+        f2 z = ld[j];
+        o[j] = z;
+        m = fmaxf(m, fmaxf(z.x, z.y));
+      }
+      m = wave_max_f32(m); /* TPL_X == 64: the line is one wave */
+      if (tl == 0) rowmax[lid] = m;
     }
     __syncthreads(); /* LDS reused next group */
   }
@@ -1000,8 +1016,8 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_fwd_m(
 }
 
 __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv_m(
-    const f2 *in, float *out, int n, unsigned long long fh, long cxp,
-    long nlines, const f2 *twg) {
+    const f2 *in, float *out, float *rowmax, int n, unsigned long long fh,
+    long cxp, long nlines, const f2 *twg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = n >> 1;
   f2 *tw = (f2 *)smem;
@@ -1035,8 +1051,14 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv_m(
     f2 *ld = (res ? db : da);
     if (active) {
       f2 *o = (f2 *)(out + lid * n);
-      for (int j = tl; j < h; j += TPL_X)
-        o[j] = ld[(long)j * LPB_X + line];
+      float m = -3.0e38f;
+      for (int j = tl; j < h; j += TPL_X) {
+        f2 z = ld[(long)j * LPB_X + line];
+        o[j] = z;
+        m = fmaxf(m, fmaxf(z.x, z.y));
+      }
+      m = wave_max_f32(m);
+      if (tl == 0) rowmax[lid] = m;
     }
     __syncthreads();
   }
@@ -1216,7 +1238,8 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_fwd_w(
  * construction, one wave per line, natural-order float2 row writes. */
 template <int E>
 __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
-    const f2 *in, float *out, long cxp, long nlines, const f2 *twg) {
+    const f2 *in, float *out, float *rowmax, long cxp, long nlines,
+    const f2 *twg) {
   constexpr int h = 64 * E, log2h = 6 + (E == 2) + 2 * (E == 4) + 3 * (E == 8);
   __shared__ f2 tw[h / 2];
   __shared__ f2 twn[h];
@@ -1245,6 +1268,11 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
 #pragma unroll
     for (int e = 0; e < E; ++e)
       o[e * 64 + lane] = v[e]; /* (pcm[2p], pcm[2p+1]) */
+    float m = fmaxf(v[0].x, v[0].y);
+#pragma unroll
+    for (int e = 1; e < E; ++e) m = fmaxf(m, fmaxf(v[e].x, v[e].y));
+    m = wave_max_f32(m);
+    if (lane == 0) rowmax[lid] = m;
   }
 }
 
@@ -1499,6 +1527,160 @@ __global__ __launch_bounds__(256) void k_peak_merge(const bs_peak *wgbuf,
     bs_peak *o = out + (long)blockIdx.x * 5;
     for (int k = 0; k < 5; ++k) o[k] = {tv[k], 0, ti[k]};
   }
+}
+
+/* ---- peak prefilter: top five from row maxima ----
+ * The inverse x pass leaves max(row) for every PCM row in rowmax
+ * (pz*py floats). A row is DOMINANT if its maximum is strictly greater
+ * than those of its 8 periodic (y,z)-neighbour rows; d5 = the fifth
+ * largest dominant maximum. Every strict local maximum with value >= d5
+ * lies in a row with rowmax >= d5 (the set R), so checking only those
+ * rows exhaustively finds all of them (the set L); with |L| >= 5 the top
+ * five of L are the global top five. The host falls back to the full
+ * scan when |L| < 5 or |R| exceeds BS_PEAK_ROWS_CAP. */
+
+#define BS_PEAK_ROWS_CAP 512  /* cost guard on |R|, not a correctness bound */
+#define BS_PEAK_ROWS_WG 256   /* blocks per prefilter kernel: 256*5 entries
+                                 merge in ONE k_peak_merge block */
+
+/* block-level merge shared by the prefilter kernels: wave shuffle merge,
+ * cross-wave merge through LDS; the block's top five end up in thread 0.
+ * A second call in the same kernel needs a __syncthreads() in between. */
+__device__ __forceinline__ void pk_block_merge(float (&tv)[5],
+                                               long long (&ti)[5]) {
+  __shared__ float wvs[4][5];
+  __shared__ long long wis[4][5];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  pk_merge_shfl(tv, ti);
+  if (lane == 0)
+    for (int k = 0; k < 5; ++k) { wvs[wv][k] = tv[k]; wis[wv][k] = ti[k]; }
+  __syncthreads();
+  if (tid == 0)
+    for (int w = 1; w < 4; ++w)
+      for (int k = 0; k < 5; ++k) pk_insert(tv, ti, wvs[w][k], wis[w][k]);
+}
+
+/* ... and on to wgbuf[5*blockIdx.x] */
+__device__ __forceinline__ void pk_block_store(float (&tv)[5],
+                                               long long (&ti)[5],
+                                               bs_peak *wgbuf) {
+  pk_block_merge(tv, ti);
+  if (threadIdx.x == 0) {
+    bs_peak *o = wgbuf + (long)blockIdx.x * 5;
+    for (int k = 0; k < 5; ++k) o[k] = {tv[k], 0, ti[k]};
+  }
+}
+
+/* Row maxima of a materialised volume (bs_debug_peak_scan only: the
+ * stitch path gets them from the inverse x pass). One wave per row. */
+__global__ __launch_bounds__(256) void k_rowmax_ref(const float *pcm, int px,
+                                                    long nrows,
+                                                    float *rowmax) {
+  const int lane = threadIdx.x & 63;
+  for (long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows;
+       r += (long)gridDim.x * 4) {
+    float m = -3.0e38f;
+    for (int x = lane; x < px; x += 64) m = fmaxf(m, pcm[r * px + x]);
+    m = wave_max_f32(m);
+    if (lane == 0) rowmax[r] = m;
+  }
+}
+
+/* Dominant rows: one thread per row, per-block top five of
+ * (rowmax, row) over rows whose maximum beats all 8 neighbour rows.
+ * Also clears the row check's |L|, |R| counters (it runs next in stream
+ * order), which saves a memset in the launch-latency-bound chain. */
+__global__ __launch_bounds__(256) void k_peak_rowdom(const float *rowmax,
+                                                     int py, int pz,
+                                                     bs_peak *wgbuf,
+                                                     int *cnt) {
+  if (blockIdx.x == 0 && threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  float tv[5];
+  long long ti[5];
+  for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
+  const long nrows = (long)py * pz;
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < nrows;
+       r += (long)gridDim.x * 256) {
+    const int y = (int)(r % py), z = (int)(r / py);
+    const float v = rowmax[r];
+    float m = -3.0e38f;
+    for (int dz = -1; dz <= 1; ++dz)
+      for (int dy = -1; dy <= 1; ++dy) {
+        if (!dy && !dz) continue;
+        const int yy = (y + dy + py) % py, zz = (z + dz + pz) % pz;
+        m = fmaxf(m, rowmax[(long)zz * py + yy]);
+      }
+    if (v > m) pk_insert(tv, ti, v, r);
+  }
+  pk_block_store(tv, ti, wgbuf);
+}
+
+/* Row check: exhaustive strict-26-maxima test (same comparison as
+ * k_peak_generic) of the elements >= d5 in the rows with rowmax >= d5.
+ * Every block first merges k_peak_rowdom's ndom per-block lists itself
+ * (a few KB from L2; one launch less than a merge kernel in between):
+ * d5 = the fifth value, a sentinel when fewer than five rows are
+ * dominant, and then nothing is checked and |L| stays 0. A wave
+ * takes 64 rows per step, ballots the qualifying ones and walks them one
+ * at a time. cnt[0] += |L|, cnt[1] += |R|; past `cap` qualifying rows
+ * the rows are only counted, so a failing prefilter stays cheap. */
+__global__ __launch_bounds__(256) void k_peak_rowcheck(
+    const float *pcm, const float *rowmax, int px, int py, int pz,
+    const bs_peak *dom, int ndom, int cap, bs_peak *wgbuf, int *cnt) {
+  __shared__ float sd5;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float tv[5];
+  long long ti[5];
+  for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
+  for (int i = tid; i < ndom; i += 256) {
+    const bs_peak p = dom[i];
+    if (p.v > -2.0e38f) pk_insert(tv, ti, p.v, p.idx);
+  }
+  pk_block_merge(tv, ti);
+  if (tid == 0) sd5 = tv[4];
+  __syncthreads();
+  const float d5 = sd5;
+  for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
+  const long nrows = (long)py * pz;
+  int nl = 0;
+  if (d5 > -2.0e38f) {
+    const long nwaves = (long)gridDim.x * 4;
+    for (long r0 = ((long)blockIdx.x * 4 + wv) * 64; r0 < nrows;
+         r0 += nwaves * 64) {
+      const long rl = r0 + lane;
+      unsigned long long mask = __ballot(rl < nrows && rowmax[rl] >= d5);
+      while (mask) { /* wave-uniform */
+        const long row = r0 + (__ffsll((long long)mask) - 1);
+        mask &= mask - 1;
+        int seen = 0;
+        if (lane == 0) seen = atomicAdd(&cnt[1], 1);
+        seen = __shfl(seen, 0);
+        if (seen >= cap) continue;
+        const int y = (int)(row % py), z = (int)(row / py);
+        for (int x = lane; x < px; x += 64) {
+          const float v = pcm[row * px + x];
+          if (!(v >= d5)) continue;
+          float m = -3.0e38f;
+          for (int dz = -1; dz <= 1; ++dz)
+            for (int dy = -1; dy <= 1; ++dy)
+              for (int dx = -1; dx <= 1; ++dx) {
+                if (!dx && !dy && !dz) continue;
+                const int xx = (x + dx + px) % px;
+                const int yy = (y + dy + py) % py;
+                const int zz = (z + dz + pz) % pz;
+                m = fmaxf(m, pcm[((long)zz * py + yy) * px + xx]);
+              }
+          if (v > m) {
+            pk_insert(tv, ti, v, row * px + x);
+            ++nl;
+          }
+        }
+      }
+    }
+  }
+  for (int off = 32; off >= 1; off >>= 1) nl += __shfl_down(nl, off);
+  if (lane == 0 && nl) atomicAdd(&cnt[0], nl);
+  pk_block_store(tv, ti, wgbuf);
 }
 
 /* 7-point PCM gather per peak for the sub-pixel fit [PIN-SUB]:
@@ -2205,7 +2387,10 @@ struct bs_slot {
   bs_peak *wgpk = nullptr;
   size_t wgpk_cap = 0;
   bs_peak *dmerge = nullptr;
-  bs_peak *dtop5 = nullptr;
+  bs_peak *dtop5 = nullptr;  /* top five + one entry of counters */
+  float *rowmax = nullptr;   /* prefilter: Pz*Py row maxima of pcm */
+  size_t rowmax_cap = 0;
+  int pk_prefilter = 0;      /* this pair's top five came from the prefilter */
   bs_cand *dcands = nullptr;
   u64 *dsums = nullptr;
   long long *dpkidx = nullptr;
@@ -2255,7 +2440,9 @@ struct bs_ctx {
   void *dvol_arena = nullptr; /* cached fuse_volume level buffers */
   size_t dvol_cap = 0;
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
+  int peak_full = 0; /* BS_PEAK_MODE=full: always the full peak scan */
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
+  bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
   long dbg_px = 0, dbg_py = 0, dbg_pz = 0;
   /* stats */
   bs_batch_stats stats{};
@@ -2308,6 +2495,8 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
     int v = atoi(e);
     if (v >= 1 && v <= BS_NSLOTS) c->nslots = v;
   }
+  if (const char *e = getenv("BS_PEAK_MODE")) /* auto (default) | full */
+    c->peak_full = strcmp(e, "full") == 0;
   if (hipSetDevice(device_id) != hipSuccess ||
       hipStreamCreate(&c->stream) != hipSuccess ||
       hipStreamCreate(&c->copy_stream) != hipSuccess) {
@@ -2366,12 +2555,12 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
          hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) ==
              hipSuccess &&
          hipMalloc(&sl.dmerge, 64 * 5 * sizeof(bs_peak)) == hipSuccess &&
-         hipMalloc(&sl.dtop5, 5 * sizeof(bs_peak)) == hipSuccess &&
+         hipMalloc(&sl.dtop5, 6 * sizeof(bs_peak)) == hipSuccess &&
          hipMalloc(&sl.dcands, 64 * sizeof(bs_cand)) == hipSuccess &&
          hipMalloc(&sl.dsums, 64 * 5 * sizeof(u64)) == hipSuccess &&
          hipMalloc(&sl.dpkidx, 8 * sizeof(long long)) == hipSuccess &&
          hipMalloc(&sl.dsubpix, 8 * 7 * sizeof(float)) == hipSuccess &&
-         hipHostMalloc(&sl.htop5, 5 * sizeof(bs_peak)) == hipSuccess &&
+         hipHostMalloc(&sl.htop5, 6 * sizeof(bs_peak)) == hipSuccess &&
          hipHostMalloc(&sl.hsums, 64 * 5 * sizeof(u64)) == hipSuccess &&
          hipHostMalloc(&sl.hsubpix, 8 * 7 * sizeof(float)) == hipSuccess;
   }
@@ -2408,6 +2597,7 @@ extern "C" void bs_ctx_destroy(bs_ctx *c) {
     (void)hipFree(sl.wgpk);
     (void)hipFree(sl.dmerge);
     (void)hipFree(sl.dtop5);
+    (void)hipFree(sl.rowmax);
     (void)hipFree(sl.dcands);
     (void)hipFree(sl.dsums);
     (void)hipFree(sl.dpkidx);
@@ -2717,6 +2907,106 @@ static int next_pow2(int n) {
 
 /* ---- stitching ---- */
 
+/* ---- peak stage [PIN-MAX]: shared by the stitch path and
+ * bs_debug_peak_scan. Needs sl->pcm, sl->rowmax and sl->Px/Py/Pz. ---- */
+
+static long peak_full_wgs(const bs_slot *sl) {
+  long ntiles = (long)((sl->Px + 255) / 256) * ((sl->Py + 3) / 4) *
+                ((sl->Pz + PKW_CZ - 1) / PKW_CZ);
+  return std::min(2048L, ntiles);
+}
+
+/* per-pair peak workspace: per-WG top-5 lists (full scan or prefilter,
+ * never both in flight) and the row maxima */
+static int peak_ensure(bs_ctx *c, bs_slot *sl) {
+  long nwg = std::max(peak_full_wgs(sl), 2L * BS_PEAK_ROWS_WG);
+  int rc = ensure_dev(c, (void **)&sl->wgpk, &sl->wgpk_cap,
+                      (size_t)nwg * 5 * sizeof(bs_peak));
+  if (rc) return rc;
+  return ensure_dev(c, (void **)&sl->rowmax, &sl->rowmax_cap,
+                    (size_t)sl->Pz * sl->Py * sizeof(float));
+}
+
+/* today's full-volume scan + hierarchical merge -> dtop5[0..4] */
+static void peak_launch_full(bs_ctx *c, bs_slot *sl) {
+  const int Px = sl->Px, Py = sl->Py, Pz = sl->Pz;
+  const long npkwg = peak_full_wgs(sl);
+  {
+    bs_tim tt(c, BS_K_PEAK, sl->stream);
+    static const bool pk_relax = getenv("BS_PEAK_RELAX") != nullptr;
+    if (Px % 4 != 0)
+      hipLaunchKernelGGL(k_peak_generic, dim3(npkwg), dim3(256), 0,
+                         sl->stream, sl->pcm, Px, Py, Pz, sl->wgpk);
+    else if (pk_relax)
+      hipLaunchKernelGGL(k_peak_tile_relaxed, dim3(npkwg), dim3(256), 0,
+                         sl->stream, sl->pcm, Px, Py, Pz, sl->wgpk);
+    else
+      hipLaunchKernelGGL(k_peak_tile, dim3(npkwg), dim3(256), 0, sl->stream,
+                         sl->pcm, Px, Py, Pz, sl->wgpk);
+  }
+  {
+    bs_tim tt(c, BS_K_PEAK_MERGE, sl->stream);
+    long nent = npkwg * 5;
+    int nb1 = (int)std::min(64L, (nent + 1279) / 1280);
+    hipLaunchKernelGGL(k_peak_merge, dim3(nb1), dim3(256), 0, sl->stream,
+                       sl->wgpk, nent, sl->dmerge);
+    hipLaunchKernelGGL(k_peak_merge, dim3(1), dim3(256), 0, sl->stream,
+                       sl->dmerge, (long)nb1 * 5, sl->dtop5);
+  }
+}
+
+/* prefilter chain: dominant rows -> (d5 +) row check -> dtop5[0..4], with
+ * |L| and |R| in the two ints at dtop5[5]. Three small launches, timed
+ * as one BS_K_PEAK_ROWS interval. wgpk holds the dominant lists in its
+ * first BS_PEAK_ROWS_WG*5 entries and the row check's lists after them. */
+static void peak_launch_rows(bs_ctx *c, bs_slot *sl) {
+  const long nrows = (long)sl->Py * sl->Pz;
+  int *cnt = (int *)(sl->dtop5 + 5);
+  bs_peak *chk = sl->wgpk + BS_PEAK_ROWS_WG * 5;
+  bs_tim tt(c, BS_K_PEAK_ROWS, sl->stream);
+  const int nb = (int)std::min((long)BS_PEAK_ROWS_WG, (nrows + 255) / 256);
+  hipLaunchKernelGGL(k_peak_rowdom, dim3(nb), dim3(256), 0, sl->stream,
+                     sl->rowmax, sl->Py, sl->Pz, sl->wgpk, cnt);
+  hipLaunchKernelGGL(k_peak_rowcheck, dim3(nb), dim3(256), 0, sl->stream,
+                     sl->pcm, sl->rowmax, sl->Px, sl->Py, sl->Pz, sl->wgpk,
+                     nb * 5, BS_PEAK_ROWS_CAP, chk, cnt);
+  hipLaunchKernelGGL(k_peak_merge, dim3(1), dim3(256), 0, sl->stream, chk,
+                     (long)nb * 5, sl->dtop5);
+}
+
+/* issue the peak stage on the slot's stream and the copy of its result;
+ * records sl->peaks_ready */
+static int peak_issue(bs_ctx *c, bs_slot *sl, bool full) {
+  sl->pk_prefilter = !full;
+  if (full) {
+    peak_launch_full(c, sl);
+  } else {
+    peak_launch_rows(c, sl);
+  }
+  /* the prefilter's |L|, |R| ride in a sixth entry; the full scan
+   * writes (and the host then reads) only the five */
+  CHK(c, hipMemcpyAsync(sl->htop5, sl->dtop5,
+                        (full ? 5 : 6) * sizeof(bs_peak),
+                        hipMemcpyDeviceToHost, sl->stream));
+  CHK(c, hipEventRecord(sl->peaks_ready, sl->stream));
+  return BS_OK;
+}
+
+/* wait for the top five; a prefilter result is accepted when |L| >= 5
+ * and |R| <= cap, otherwise the full scan runs now and is waited for */
+static int peak_resolve(bs_ctx *c, bs_slot *sl, int *fell_back) {
+  CHK(c, hipEventSynchronize(sl->peaks_ready));
+  if (fell_back) *fell_back = 0;
+  if (!sl->pk_prefilter) return BS_OK;
+  const int *cnt = (const int *)(sl->htop5 + 5); /* |L|, |R| */
+  if (cnt[0] >= 5 && cnt[1] <= BS_PEAK_ROWS_CAP) return BS_OK;
+  if (fell_back) *fell_back = 1;
+  int rc = peak_issue(c, sl, true);
+  if (rc) return rc;
+  CHK(c, hipEventSynchronize(sl->peaks_ready));
+  return BS_OK;
+}
+
 /* ---- stitching pipeline (two slots, see bs_slot) ---- */
 
 /* Phase A: validate + downsample + FFT chain + peak scan for one pair;
@@ -2795,6 +3085,8 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
   if (rc) return rc;
   size_t pcm_n = (size_t)Pz * Py * Px;
   rc = ensure_dev(c, (void **)&sl->pcm, &sl->pcm_cap, pcm_n * sizeof(float));
+  if (rc) return rc;
+  rc = peak_ensure(c, sl);
   if (rc) return rc;
   f2 *twx = is_pow2(Px) ? get_twiddle(c, Px) : get_twiddle_full(c, Px);
   f2 *twy = is_pow2(Py) ? get_twiddle(c, Py) : get_twiddle_full(c, Py);
@@ -2936,67 +3228,38 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
       size_t lds = ((Px / 2) + 2 * (size_t)LPB_X * (Px / 2)) * sizeof(f2);
       hipLaunchKernelGGL(k_fft_x_inv_m, dim3(std::min(4096L, ngrp)),
                          dim3(LPB_X * TPL_X), lds, sl->stream, spec[0],
-                         sl->pcm, Px, bs_factorize(Px / 2), Cxp, nlines,
-                         twx);
+                         sl->pcm, sl->rowmax, Px, bs_factorize(Px / 2), Cxp,
+                         nlines, twx);
     } else if (Px >= 128 && Px <= 1024) { /* wave-resident fast path */
       long ngrp = (nlines + XW_WPB - 1) / XW_WPB;
       dim3 g(std::min(4096L, ngrp)), b(64 * XW_WPB);
       if (Px == 128)
         hipLaunchKernelGGL(k_fft_x_inv_w<1>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, Cxp, nlines, twx);
+                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
       else if (Px == 256)
         hipLaunchKernelGGL(k_fft_x_inv_w<2>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, Cxp, nlines, twx);
+                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
       else if (Px == 512)
         hipLaunchKernelGGL(k_fft_x_inv_w<4>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, Cxp, nlines, twx);
+                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
       else
         hipLaunchKernelGGL(k_fft_x_inv_w<8>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, Cxp, nlines, twx);
+                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
     } else {
       long ngrp = (nlines + LPB_X - 1) / LPB_X;
       size_t lds = ((Px / 4) + (size_t)LPB_X * (Px / 2)) * sizeof(f2);
       hipLaunchKernelGGL(k_fft_x_inv, dim3(std::min(4096L, ngrp)),
                          dim3(LPB_X * TPL_X), lds, sl->stream, spec[0],
-                         sl->pcm, Px, ilog2(Px), Cx, Cxp, nlines, twx);
+                         sl->pcm, sl->rowmax, Px, ilog2(Px), Cx, Cxp, nlines,
+                         twx);
     }
   }
   c->dbg_pcm = sl->pcm;
   c->dbg_px = Px;
   c->dbg_py = Py;
   c->dbg_pz = Pz;
-  /* peak scan [PIN-MAX] */
-  long ntiles = (long)((Px + 255) / 256) * ((Py + 3) / 4) *
-                ((Pz + PKW_CZ - 1) / PKW_CZ);
-  long npkwg = std::min(2048L, ntiles);
-  int rc2 = ensure_dev(c, (void **)&sl->wgpk, &sl->wgpk_cap,
-                       (size_t)npkwg * 5 * sizeof(bs_peak));
-  if (rc2) return rc2;
-  {
-    bs_tim tt(c, BS_K_PEAK, sl->stream);
-    static const bool pk_relax = getenv("BS_PEAK_RELAX") != nullptr;
-    if (Px % 4 != 0)
-      hipLaunchKernelGGL(k_peak_generic, dim3(npkwg), dim3(256), 0,
-                         sl->stream, sl->pcm, Px, Py, Pz, sl->wgpk);
-    else if (pk_relax)
-      hipLaunchKernelGGL(k_peak_tile_relaxed, dim3(npkwg), dim3(256), 0,
-                         sl->stream, sl->pcm, Px, Py, Pz, sl->wgpk);
-    else
-      hipLaunchKernelGGL(k_peak_tile, dim3(npkwg), dim3(256), 0, sl->stream,
-                         sl->pcm, Px, Py, Pz, sl->wgpk);
-  }
-  {
-    bs_tim tt(c, BS_K_PEAK_MERGE, sl->stream);
-    long nent = npkwg * 5;
-    int nb1 = (int)std::min(64L, (nent + 1279) / 1280);
-    hipLaunchKernelGGL(k_peak_merge, dim3(nb1), dim3(256), 0, sl->stream,
-                       sl->wgpk, nent, sl->dmerge);
-    hipLaunchKernelGGL(k_peak_merge, dim3(1), dim3(256), 0, sl->stream,
-                       sl->dmerge, (long)nb1 * 5, sl->dtop5);
-  }
-  CHK(c, hipMemcpyAsync(sl->htop5, sl->dtop5, 5 * sizeof(bs_peak),
-                        hipMemcpyDeviceToHost, sl->stream));
-  CHK(c, hipEventRecord(sl->peaks_ready, sl->stream));
+  rc = peak_issue(c, sl, c->peak_full != 0);
+  if (rc) return rc;
   sl->stage = 1;
   return BS_OK;
 }
@@ -3005,7 +3268,9 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
  * [PIN-CAND], launch r-test + sub-pixel gather; records sl->done. */
 static int stitch_phaseB(bs_ctx *c, bs_slot *sl,
                          const bs_stitch_params *prm) {
-  CHK(c, hipEventSynchronize(sl->peaks_ready));
+  int rc = peak_resolve(c, sl, nullptr);
+  if (rc) return rc;
+  std::memcpy(c->dbg_top5, sl->htop5, sizeof(c->dbg_top5));
   const int K = prm->peaks_to_check > 0 ? prm->peaks_to_check : 5;
   if (getenv("BS_DEBUG_PEAKS")) {
     for (int k = 0; k < 5; ++k) {
@@ -3210,6 +3475,64 @@ extern "C" int bs_debug_pcm(bs_ctx *c, float *out, int64_t out_dims[3]) {
   if (!n) return BS_EINVAL;
   if (!c->dbg_pcm) return BS_EINVAL;
   CHK(c, hipMemcpy(out, c->dbg_pcm, n * 4, hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
+/* Debug-only: the LAST pair's top five exactly as phase B consumed them
+ * (after the prefilter's acceptance test or its fallback). */
+extern "C" int bs_debug_last_top5(bs_ctx *c, float v[5], int64_t idx[5]) {
+  if (!c || !v || !idx) return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int k = 0; k < 5; ++k) {
+    v[k] = c->dbg_top5[k].v;
+    idx[k] = c->dbg_top5[k].idx;
+  }
+  return BS_OK;
+}
+
+/* Debug-only: run the peak stage of the stitch path (prefilter,
+ * acceptance, fallback — the same peak_issue/peak_resolve) on a
+ * caller-supplied float volume, dims = {px, py, pz}. mode 0 = auto,
+ * 1 = full. Row maxima come from k_rowmax_ref instead of the inverse x
+ * pass. Uses slot 0's workspace; call between batches. */
+extern "C" int bs_debug_peak_scan(bs_ctx *c, const float *pcm_host,
+                                  const int64_t dims[3], int mode,
+                                  float v[5], int64_t idx[5],
+                                  int *fell_back) {
+  if (!c || !pcm_host || !dims || !v || !idx) return BS_EINVAL;
+  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || dims[0] > 1024 ||
+      dims[1] > 1024 || dims[2] > 1024 || (mode != 0 && mode != 1))
+    return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  CHK(c, hipSetDevice(c->dev));
+  bs_slot *sl = &c->slot[0];
+  sl->Px = (int)dims[0];
+  sl->Py = (int)dims[1];
+  sl->Pz = (int)dims[2];
+  const long nrows = (long)sl->Py * sl->Pz;
+  const size_t n = (size_t)nrows * sl->Px;
+  int rc = ensure_dev(c, (void **)&sl->pcm, &sl->pcm_cap, n * sizeof(float));
+  if (rc) return rc;
+  c->dbg_pcm = sl->pcm;
+  c->dbg_px = sl->Px;
+  c->dbg_py = sl->Py;
+  c->dbg_pz = sl->Pz;
+  rc = peak_ensure(c, sl);
+  if (rc) return rc;
+  CHK(c, hipMemcpyAsync(sl->pcm, pcm_host, n * sizeof(float),
+                        hipMemcpyHostToDevice, sl->stream));
+  hipLaunchKernelGGL(k_rowmax_ref, dim3(std::min(1024L, (nrows + 3) / 4)),
+                     dim3(256), 0, sl->stream, sl->pcm, sl->Px, nrows,
+                     sl->rowmax);
+  rc = peak_issue(c, sl, mode == 1);
+  if (rc == BS_OK) rc = peak_resolve(c, sl, fell_back);
+  CHK(c, hipStreamSynchronize(sl->stream));
+  flush_stats(c);
+  if (rc) return rc;
+  for (int k = 0; k < 5; ++k) {
+    v[k] = sl->htop5[k].v;
+    idx[k] = sl->htop5[k].idx;
+  }
   return BS_OK;
 }
 

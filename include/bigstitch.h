@@ -248,6 +248,23 @@ int bs_fuse_volume(bs_ctx *ctx, const bs_fuse_view *views, size_t nviews,
  * geometry). Not part of the drop-in surface; used by parity tooling. */
 int bs_debug_pcm(bs_ctx *ctx, float *out, int64_t out_dims[3]);
 
+/* Debug-only: the top five PCM maxima (value, linear index) of the LAST
+ * pair processed by bs_stitch_batch, exactly as the candidate stage
+ * received them. Missing entries carry the scan's sentinel
+ * (v = -3e38, idx = INT64_MAX). */
+int bs_debug_last_top5(bs_ctx *ctx, float v[5], int64_t idx[5]);
+
+/* Debug-only: run the stitch path's peak stage on a caller-supplied
+ * float volume (dims = {px, py, pz}, x fastest). mode 0 = auto (row-maxima
+ * prefilter with the full scan as fallback), 1 = full scan. fell_back
+ * (optional) receives 1 when the prefilter's result was rejected and the
+ * full scan ran. The mode of bs_stitch_batch itself is fixed per context
+ * by the environment variable BS_PEAK_MODE (auto | full) read in
+ * bs_ctx_create. */
+int bs_debug_peak_scan(bs_ctx *ctx, const float *pcm_host,
+                       const int64_t dims[3], int mode, float v[5],
+                       int64_t idx[5], int *fell_back);
+
 /* ------------------------------------------------------- instrumentation */
 
 /* Per-kernel timing, HIP-event measured on the launch stream (bench.py
@@ -268,6 +285,8 @@ enum bs_kernel_id {
   BS_K_FUSE,       /* inverse-affine trilinear blend fusion */
   BS_K_SYNTH,      /* bench-only synthetic tile render */
   BS_K_PYRAMID,    /* 2x (or general) box-mean pyramid level */
+  BS_K_PEAK_ROWS,  /* peak prefilter chain (row maxima -> top five);
+                      BS_K_PEAK/_MERGE then count only fallback scans */
   BS_K_COUNT
 };
 
