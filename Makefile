@@ -29,7 +29,7 @@ HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall
 $(HOSTDIR)/%.o: $(HOSTDIR)/%.cpp $(HOSTDIR)/%.h
 	$(CXX_HOST) $(HOSTFLAGS) -c $< -o $@
 
-cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave
+cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave $(BINDIR)/detect-interestpoints
 
 $(BINDIR)/stitching: $(HOSTDIR)/cli_stitching.cpp $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
@@ -48,6 +48,10 @@ $(BINDIR)/solver: $(HOSTDIR)/cli_solver.cpp $(HOSTOBJS)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -lz -l:libzstd.so.1
 
 $(BINDIR)/resave: $(HOSTDIR)/cli_resave.cpp $(HOSTOBJS) $(LIB)
+	@mkdir -p $(BINDIR)
+	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+
+$(BINDIR)/detect-interestpoints: $(HOSTDIR)/cli_detect.cpp $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
@@ -71,5 +75,6 @@ asan:
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_stitching.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/stitching -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_fusion.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/affine-fusion -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_resave.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/resave -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_detect.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/detect-interestpoints -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
 .PHONY: asan

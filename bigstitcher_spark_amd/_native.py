@@ -62,10 +62,37 @@ class _FuseParams(C.Structure):
     ]
 
 
+class _DogParams(C.Structure):
+    _fields_ = [
+        ("sigma", C.c_double), ("threshold", C.c_double),
+        ("min_intensity", C.c_double), ("max_intensity", C.c_double),
+        ("find_min", C.c_int32), ("find_max", C.c_int32),
+        ("localization", C.c_int32), ("ds", C.c_int32 * 3),
+    ]
+
+
+class _InterestPoint(C.Structure):
+    _fields_ = [
+        ("loc", C.c_double * 3), ("value", C.c_float),
+        ("intensity", C.c_float), ("kind", C.c_int32),
+        ("converged", C.c_int32),
+    ]
+
+
+# numpy view of bs_interest_point[] (same layout as _InterestPoint)
+_IP_DTYPE = np.dtype([("loc", np.float64, 3), ("value", np.float32),
+                      ("intensity", np.float32), ("kind", np.int32),
+                      ("converged", np.int32)])
+assert _IP_DTYPE.itemsize == C.sizeof(_InterestPoint)
+
+LOCALIZATION = {"none": 0, "quadratic": 1}
+
+
 BS_K_NAMES = [
     "downsample", "fft_x_fwd", "fft_y_fwd", "fft_z_fwd", "fft_z_inv",
     "fft_y_inv", "fft_x_inv", "peak", "peak_merge", "corr", "subpix",
     "fuse", "synth", "pyramid", "peak_rows",
+    "dog_xy", "dog_z", "dog_extrema", "dog_subpix",
 ]
 _NK = len(BS_K_NAMES)
 
@@ -138,6 +165,12 @@ def load_lib():
     lib.bs_debug_peak_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3,
                                        C.c_int, C.c_float * 5, C.c_int64 * 5,
                                        C.POINTER(C.c_int)]
+    lib.bs_detect_dog.argtypes = [C.c_void_p, C.c_int32,
+                                  C.POINTER(_DogParams), C.c_void_p,
+                                  C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.bs_debug_dog_volume.argtypes = [C.c_void_p, C.c_int32,
+                                        C.POINTER(_DogParams), C.c_void_p,
+                                        C.c_int64 * 3]
     _lib = lib
     return lib
 
@@ -354,6 +387,64 @@ class Context:
             "bs_fuse_volume",
         )
         return outs
+
+    # -- interest point detection -----------------------------------------
+    @staticmethod
+    def _dog_params(sigma, threshold, min_intensity, max_intensity,
+                    find_min, find_max, localization, ds):
+        return _DogParams(float(sigma), float(threshold),
+                          float(min_intensity), float(max_intensity),
+                          int(bool(find_min)), int(bool(find_max)),
+                          LOCALIZATION[localization.lower()],
+                          (C.c_int32 * 3)(*[int(f) for f in ds]))
+
+    def detect_dog_raw(self, view_id, prm, capacity):
+        """ABI-level call: (structured array of min(n_found, capacity)
+        points, n_found)."""
+        out = np.zeros(capacity, _IP_DTYPE)
+        n = C.c_size_t(0)
+        self._check(
+            self._lib.bs_detect_dog(
+                self._h, view_id, C.byref(prm),
+                out.ctypes.data_as(C.c_void_p) if capacity else None,
+                capacity, C.byref(n)),
+            "bs_detect_dog",
+        )
+        return out[:min(capacity, n.value)], int(n.value)
+
+    def detect_dog(self, view_id, sigma, threshold, min_intensity,
+                   max_intensity, find_min=False, find_max=True,
+                   localization="quadratic", ds=(1, 1, 1)):
+        """Difference-of-Gaussian interest points of an uploaded view.
+        ds: residual box-mean factors (x,y,z). Returns a dict of arrays:
+        loc (N,3) float64 in xyz view pixels, value, intensity (float32),
+        kind (+1 max / -1 min), converged (int32); sorted by final voxel."""
+        prm = self._dog_params(sigma, threshold, min_intensity,
+                               max_intensity, find_min, find_max,
+                               localization, ds)
+        _, n = self.detect_dog_raw(view_id, prm, 0)
+        pts, n2 = self.detect_dog_raw(view_id, prm, n)
+        if n2 != n:
+            raise RuntimeError(f"bs_detect_dog: count changed {n} -> {n2}")
+        return {k: np.ascontiguousarray(pts[k]) for k in _IP_DTYPE.names}
+
+    def debug_dog_volume(self, view_id, sigma, min_intensity, max_intensity,
+                         ds=(1, 1, 1)):
+        """The DoG volume D at detection scale, (nz, ny, nx) float32."""
+        prm = self._dog_params(sigma, 0.0, min_intensity, max_intensity,
+                               False, True, "none", ds)
+        dims = (C.c_int64 * 3)()
+        self._check(self._lib.bs_debug_dog_volume(self._h, view_id,
+                                                  C.byref(prm), None, dims),
+                    "bs_debug_dog_volume")
+        out = np.empty((dims[2], dims[1], dims[0]), np.float32)
+        self._check(
+            self._lib.bs_debug_dog_volume(
+                self._h, view_id, C.byref(prm),
+                out.ctypes.data_as(C.c_void_p), dims),
+            "bs_debug_dog_volume",
+        )
+        return out
 
     # -- debug (not part of the product surface) --------------------------
     def debug_last_top5(self):

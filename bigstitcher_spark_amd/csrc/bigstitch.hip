@@ -7,6 +7,9 @@
  *     (reference SparkPairwiseStitching.java:247-255) -> bs_stitch_batch
  *   - BlkAffineFusion.initWithIntensityCoefficients + materializing copy
  *     (reference SparkAffineFusion.java:602-615,627)  -> bs_fuse_blocks
+ *   - DoGImgLib2.computeDoG
+ *     (reference SparkInterestPointDetection.java:552-568) -> bs_detect_dog
+ *     (contract = tests/dog_ref.py; section at the end of this file)
  *
  * Arithmetic contract = oracle/phasecorr.py and oracle/fusion.py (the CPU
  * restatement; see its [PIN-*] notes). Shifts must match the oracle within
@@ -2303,6 +2306,8 @@ struct bs_view_rec {
   int cg[3] = {0, 0, 0};
 };
 
+struct bs_dog_pt;
+
 struct bs_ev {
   hipEvent_t a, b;
   int kid;
@@ -2444,6 +2449,17 @@ struct bs_ctx {
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
   bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
   long dbg_px = 0, dbg_py = 0, dbg_pz = 0;
+  /* DoG interest-point detection scratch (bs_detect_dog) */
+  float *dog_box = nullptr, *dog_g1 = nullptr, *dog_g2 = nullptr,
+        *dog_d = nullptr;
+  size_t dog_box_cap = 0, dog_g1_cap = 0, dog_g2_cap = 0, dog_d_cap = 0;
+  long long *dog_cand = nullptr; /* 2*linear index + (minimum ? 1 : 0) */
+  size_t dog_cand_cap = 0;
+  struct bs_dog_pt *dog_pts = nullptr;
+  size_t dog_pts_cap = 0;
+  unsigned int *dog_cnt = nullptr;
+  size_t dog_cnt_cap = 0;
+  size_t dog_init_cap = 65536; /* first candidate capacity (BS_DOG_INIT_CAP) */
   /* stats */
   bs_batch_stats stats{};
   std::vector<bs_ev> evs;
@@ -2497,6 +2513,10 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   }
   if (const char *e = getenv("BS_PEAK_MODE")) /* auto (default) | full */
     c->peak_full = strcmp(e, "full") == 0;
+  if (const char *e = getenv("BS_DOG_INIT_CAP")) {
+    long v = atol(e);
+    if (v >= 1) c->dog_init_cap = (size_t)v;
+  }
   if (hipSetDevice(device_id) != hipSuccess ||
       hipStreamCreate(&c->stream) != hipSuccess ||
       hipStreamCreate(&c->copy_stream) != hipSuccess) {
@@ -2619,6 +2639,13 @@ extern "C" void bs_ctx_destroy(bs_ctx *c) {
   (void)hipFree(c->dviews);
   (void)hipFree(c->dvidx);
   (void)hipFree(c->dblobs);
+  (void)hipFree(c->dog_box);
+  (void)hipFree(c->dog_g1);
+  (void)hipFree(c->dog_g2);
+  (void)hipFree(c->dog_d);
+  (void)hipFree(c->dog_cand);
+  (void)hipFree(c->dog_pts);
+  (void)hipFree(c->dog_cnt);
   (void)hipStreamDestroy(c->stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   delete c;
@@ -4200,5 +4227,632 @@ extern "C" int bs_fuse_volume(bs_ctx *c, const bs_fuse_view *views,
   for (auto ev : slab_ev) (void)hipEventDestroy(ev);
   c->stats.blocks += (long long)fblocks.size();
   flush_stats(c);
+  return BS_OK;
+}
+
+/* ================================================================== *
+ *  Difference-of-Gaussian interest point detection (bs_detect_dog)   *
+ * ================================================================== *
+ * Arithmetic contract = tests/dog_ref.py (see the [PIN-*] list in
+ * include/bigstitch.h). Four kernels over the x-fastest volume:
+ *   k_dog_xy       tile + halo -> LDS, x then y pass for both sigmas
+ *   k_dog_z        z pass for both volumes, per-column LDS window -> D
+ *   k_dog_extrema  gate + strict 3x3x3 extremum, wave-ballot compaction
+ *   k_dog_subpix   per-candidate quadratic fit (double) + intensity
+ * plus k_dog_box (uint16 -> float box mean) when ds != {1,1,1}.        */
+
+#define DOG_RMAX 32 /* largest filter radius h-1 */
+#define DOG_WPAD 8  /* zero taps either side: the blocked y pass indexes
+                       w[j - o + DOG_WPAD] for o < DOG_YB */
+#define DOG_WLEN (2 * DOG_RMAX + 1 + 2 * DOG_WPAD)
+#define DOG_TX 64   /* xy tile */
+#define DOG_TY 32
+#define DOG_YB 8    /* y outputs per thread (register blocked) */
+#define DOG_ZC 64   /* z planes per k_dog_z block */
+
+/* Both tap sets, centred on the same index (DOG_WPAD + R) and zero
+ * outside their own radius, so one loop over -R..R serves both sigmas. */
+struct bs_dog_w {
+  float w1[DOG_WLEN];
+  float w2[DOG_WLEN];
+};
+
+struct bs_dog_pt {
+  double loc[3];       /* detection-scale x,y,z */
+  long long fin;       /* linear index of the final integer voxel */
+  long long start;     /* linear index of the candidate voxel */
+  float value, intensity;
+  int kind, converged, keep, _pad;
+};
+
+/* mirror with the edge sample repeated (numpy "symmetric"); any number of
+ * reflections */
+__device__ __forceinline__ int dog_mirror(int i, int n) {
+  const int p = 2 * n;
+  int m = i % p;
+  if (m < 0) m += p;
+  return m < n ? m : p - 1 - m;
+}
+
+__device__ __forceinline__ float dog_cvt(unsigned short v) { return (float)v; }
+__device__ __forceinline__ float dog_cvt(float v) { return v; }
+
+/* [PIN-DS2X] residual box mean, uint16 -> float, no rounding */
+__global__ __launch_bounds__(256) void k_dog_box(
+    const unsigned short *__restrict__ src, float *__restrict__ dst, int sx,
+    int sy, int nx, int ny, int nz, int fx, int fy, int fz) {
+  const long nrows = (long)ny * nz;
+  const float inv = 1.0f / (float)(fx * fy * fz);
+  for (long row = blockIdx.x; row < nrows; row += gridDim.x) {
+    const int y = (int)(row % ny), z = (int)(row / ny);
+    for (int x = threadIdx.x; x < nx; x += 256) {
+      unsigned long long s = 0;
+      for (int c = 0; c < fz; ++c)
+        for (int b = 0; b < fy; ++b) {
+          const unsigned short *r =
+              src + ((long)(z * fz + c) * sy + (y * fy + b)) * sx +
+              (long)x * fx;
+          for (int a = 0; a < fx; ++a) s += r[a];
+        }
+      dst[row * nx + x] = (float)s * inv;
+    }
+  }
+}
+
+/* x + y passes for both sigmas from one LDS tile. LDS (floats):
+ *   in  [DOG_TY + 2R][DOG_TX + 2Ra]   normalised input, Ra = R rounded up
+ *                                     to 4 so 4-element groups stay aligned
+ *   m1,m2 [DOG_TY + 2R][DOG_TX]       x-filtered rows, one per sigma
+ * Lanes run along x in every phase, so a wave always touches 64
+ * consecutive floats of one LDS row: no bank conflicts on either pass and
+ * no row padding needed. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_dog_xy(
+    const T *__restrict__ src, float *__restrict__ g1,
+    float *__restrict__ g2, int nx, int ny, int nz, float lo, float inv,
+    int R, bs_dog_w w) {
+  extern __shared__ float dog_lds[];
+  const int Ra = (R + 3) & ~3;
+  const int IW = DOG_TX + 2 * Ra;
+  const int rows = DOG_TY + 2 * R;
+  float *in = dog_lds;
+  float *m1 = in + rows * IW;
+  float *m2 = m1 + rows * DOG_TX;
+  const int tid = threadIdx.x;
+  const int ntx = (nx + DOG_TX - 1) / DOG_TX;
+  const int nty = (ny + DOG_TY - 1) / DOG_TY;
+  const long ntiles = (long)ntx * nty * nz;
+  const bool vec = (nx & 3) == 0;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int bx = (int)(tile % ntx);
+    const int by = (int)((tile / ntx) % nty);
+    const int z = (int)(tile / ((long)ntx * nty));
+    const int x0 = bx * DOG_TX, y0 = by * DOG_TY;
+    /* load + normalise: 4-element groups, vector load where the group is
+     * inside the row, mirrored scalar loads at the faces */
+    const int gpr = IW >> 2;
+    for (int g = tid; g < rows * gpr; g += 256) {
+      const int r = g / gpr, j = g - r * gpr;
+      const int gy = dog_mirror(y0 - R + r, ny);
+      const int gx = x0 - Ra + 4 * j;
+      const T *rowp = src + ((long)z * ny + gy) * nx;
+      float v0, v1, v2, v3;
+      if (vec && gx >= 0 && gx + 3 < nx) {
+        if (sizeof(T) == 2) {
+          const ushort4 q = *reinterpret_cast<const ushort4 *>(rowp + gx);
+          v0 = (float)q.x; v1 = (float)q.y; v2 = (float)q.z; v3 = (float)q.w;
+        } else {
+          const float4 q = *reinterpret_cast<const float4 *>(rowp + gx);
+          v0 = q.x; v1 = q.y; v2 = q.z; v3 = q.w;
+        }
+      } else {
+        v0 = dog_cvt(rowp[dog_mirror(gx, nx)]);
+        v1 = dog_cvt(rowp[dog_mirror(gx + 1, nx)]);
+        v2 = dog_cvt(rowp[dog_mirror(gx + 2, nx)]);
+        v3 = dog_cvt(rowp[dog_mirror(gx + 3, nx)]);
+      }
+      float *d = in + r * IW + 4 * j;
+      d[0] = (v0 - lo) * inv;
+      d[1] = (v1 - lo) * inv;
+      d[2] = (v2 - lo) * inv;
+      d[3] = (v3 - lo) * inv;
+    }
+    __syncthreads();
+    /* x pass */
+    {
+      const int tx = tid & (DOG_TX - 1);
+      for (int r = tid >> 6; r < rows; r += 4) {
+        const float *p = in + r * IW + (Ra - R) + tx;
+        float a1 = 0.0f, a2 = 0.0f;
+        for (int k = 0; k <= 2 * R; ++k) {
+          const float v = p[k];
+          a1 = fmaf(w.w1[DOG_WPAD + k], v, a1);
+          a2 = fmaf(w.w2[DOG_WPAD + k], v, a2);
+        }
+        m1[r * DOG_TX + tx] = a1;
+        m2[r * DOG_TX + tx] = a2;
+      }
+    }
+    __syncthreads();
+    /* y pass: DOG_YB consecutive outputs per thread share their inputs */
+    {
+      const int tx = tid & (DOG_TX - 1);
+      const int yb = (tid >> 6) * DOG_YB;
+      float a1[DOG_YB], a2[DOG_YB];
+#pragma unroll
+      for (int o = 0; o < DOG_YB; ++o) a1[o] = a2[o] = 0.0f;
+      for (int j = 0; j < DOG_YB + 2 * R; ++j) {
+        const float v1 = m1[(yb + j) * DOG_TX + tx];
+        const float v2 = m2[(yb + j) * DOG_TX + tx];
+#pragma unroll
+        for (int o = 0; o < DOG_YB; ++o) {
+          a1[o] = fmaf(w.w1[j - o + DOG_WPAD], v1, a1[o]);
+          a2[o] = fmaf(w.w2[j - o + DOG_WPAD], v2, a2[o]);
+        }
+      }
+      const int x = x0 + tx;
+      if (x < nx) {
+#pragma unroll
+        for (int o = 0; o < DOG_YB; ++o) {
+          const int y = y0 + yb + o;
+          if (y < ny) {
+            const long idx = ((long)z * ny + y) * nx + x;
+            g1[idx] = a1[o];
+            g2[idx] = a2[o];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+/* z pass for both volumes + [PIN-DOG-SIGN] D = (G1 - G2) * wgt. Each
+ * thread owns one (x,y) column of a DOG_ZC-plane chunk and keeps the last
+ * 2R+1 samples of both volumes in its own LDS column (a register window
+ * with a run-time length); x stays the coalesced axis. No thread reads
+ * another thread's LDS, so there are no barriers. */
+__global__ __launch_bounds__(256) void k_dog_z(
+    const float *__restrict__ g1, const float *__restrict__ g2,
+    float *__restrict__ D, int nx, int ny, int nz, int R, float wgt,
+    bs_dog_w w) {
+  extern __shared__ float dog_lds[];
+  const int L = 2 * R + 1;
+  const int tid = threadIdx.x;
+  float *r1 = dog_lds + tid;
+  float *r2 = dog_lds + L * 256 + tid;
+  const int ntx = (nx + 63) / 64, nty = (ny + 3) / 4;
+  const int nzc = (nz + DOG_ZC - 1) / DOG_ZC;
+  const long ntiles = (long)ntx * nty * nzc;
+  const long plane = (long)nx * ny;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int x = (int)(tile % ntx) * 64 + (tid & 63);
+    const int y = (int)((tile / ntx) % nty) * 4 + (tid >> 6);
+    const int z0 = (int)(tile / ((long)ntx * nty)) * DOG_ZC;
+    const int z1 = min(z0 + DOG_ZC, nz);
+    if (x >= nx || y >= ny) continue;
+    const long col = (long)y * nx + x;
+    for (int j = 0; j < 2 * R; ++j) {
+      const long o = dog_mirror(z0 - R + j, nz) * plane + col;
+      r1[j * 256] = g1[o];
+      r2[j * 256] = g2[o];
+    }
+    int head = 0; /* slot of plane z - R */
+    long on = dog_mirror(z0 + R, nz) * plane + col;
+    float n1 = g1[on], n2 = g2[on];
+    for (int z = z0; z < z1; ++z) {
+      int s = head + 2 * R;
+      if (s >= L) s -= L;
+      r1[s * 256] = n1;
+      r2[s * 256] = n2;
+      if (z + 1 < z1) { /* next plane's loads fly under this plane's sums */
+        on = dog_mirror(z + 1 + R, nz) * plane + col;
+        n1 = g1[on];
+        n2 = g2[on];
+      }
+      float a1 = 0.0f, a2 = 0.0f;
+      s = head;
+      for (int k = 0; k < L; ++k) {
+        a1 = fmaf(w.w1[DOG_WPAD + k], r1[s * 256], a1);
+        a2 = fmaf(w.w2[DOG_WPAD + k], r2[s * 256], a2);
+        if (++s == L) s = 0;
+      }
+      D[z * plane + col] = (a1 - a2) * wgt;
+      if (++head == L) head = 0;
+    }
+  }
+}
+
+/* [PIN-EXTREMA] + [PIN-THRESH] candidate scan. The gate is tested first,
+ * so the 26 neighbour loads run only for the few voxels that pass it.
+ * Compaction: one wave ballot + one atomic per wave; the counter always
+ * counts, stores stop at cap (the host then grows the buffer and relaunches
+ * this kernel only). Order is arbitrary; the host sorts. */
+__global__ __launch_bounds__(256) void k_dog_extrema(
+    const float *__restrict__ D, int nx, int ny, int nz, float gate,
+    int find_min, int find_max, long long *__restrict__ cand,
+    unsigned int cap, unsigned int *__restrict__ cnt) {
+  const long nrows = (long)(ny - 2) * (nz - 2);
+  const long plane = (long)nx * ny;
+  const int lane = threadIdx.x & 63;
+  for (long row = blockIdx.x; row < nrows; row += gridDim.x) {
+    const int y = (int)(row % (ny - 2)) + 1, z = (int)(row / (ny - 2)) + 1;
+    const float *c = D + z * plane + (long)y * nx;
+    for (int xb = 1; xb < nx - 1; xb += 256) { /* block-uniform trip count */
+      const int x = xb + threadIdx.x;
+      int kind = 0;
+      if (x < nx - 1) {
+        const float v = c[x];
+        if (fabsf(v) >= gate) {
+          bool mx = find_max != 0, mn = find_min != 0;
+          for (int dz = -1; dz <= 1 && (mx || mn); ++dz)
+            for (int dy = -1; dy <= 1; ++dy) {
+              const float *r = c + dz * plane + (long)dy * nx + x;
+#pragma unroll
+              for (int dx = -1; dx <= 1; ++dx) {
+                if (dz == 0 && dy == 0 && dx == 0) continue;
+                const float u = r[dx];
+                mx = mx && v > u;
+                mn = mn && v < u;
+              }
+            }
+          kind = mx ? 1 : (mn ? -1 : 0);
+        }
+      }
+      const unsigned long long m = __ballot(kind != 0);
+      if (m) {
+        unsigned int base = 0;
+        if (lane == __ffsll((long long)m) - 1)
+          base = atomicAdd(cnt, (unsigned int)__popcll(m));
+        base = __shfl(base, __ffsll((long long)m) - 1);
+        if (kind != 0) {
+          const unsigned int slot =
+              base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+          if (slot < cap)
+            cand[slot] = 2 * ((long long)(c - D) + x) + (kind < 0 ? 1 : 0);
+        }
+      }
+    }
+  }
+}
+
+/* [PIN-SUBPIX] one thread per candidate: iterative quadratic fit in
+ * double, final [PIN-THRESH] gate, trilinear intensity from the raw
+ * detection-scale input with border clamp. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_dog_subpix(
+    const float *__restrict__ D, const T *__restrict__ raw, int nx, int ny,
+    int nz, const long long *__restrict__ cand, unsigned int n,
+    int localization, double threshold, bs_dog_pt *__restrict__ out) {
+  const long plane = (long)nx * ny;
+  for (unsigned int i = blockIdx.x * 256 + threadIdx.x; i < n;
+       i += gridDim.x * 256) {
+    const long long code = cand[i];
+    const long long lin = code >> 1;
+    int p[3] = {(int)(lin % nx), (int)((lin / nx) % ny), (int)(lin / plane)};
+    const int p0[3] = {p[0], p[1], p[2]};
+    const int dims[3] = {nx, ny, nz};
+    const long st[3] = {1, nx, plane};
+    double o[3] = {0.0, 0.0, 0.0};
+    double value = (double)D[lin];
+    int conv = 1;
+    if (localization == 1) {
+      conv = 0;
+      for (int m = 0; m <= 10; ++m) {
+        if (p[0] < 1 || p[0] > nx - 2 || p[1] < 1 || p[1] > ny - 2 ||
+            p[2] < 1 || p[2] > nz - 2)
+          break;
+        const float *q = D + (long)p[2] * plane + (long)p[1] * nx + p[0];
+        const double v = (double)q[0];
+        double g[3], H[3][3];
+        for (int d = 0; d < 3; ++d) {
+          const double a = (double)q[st[d]], b = (double)q[-st[d]];
+          g[d] = 0.5 * (a - b);
+          H[d][d] = a - 2.0 * v + b;
+        }
+        for (int d = 0; d < 3; ++d)
+          for (int e = d + 1; e < 3; ++e)
+            H[d][e] = H[e][d] =
+                0.25 * ((double)q[st[d] + st[e]] - (double)q[st[d] - st[e]] -
+                        (double)q[-st[d] + st[e]] + (double)q[-st[d] - st[e]]);
+        const double c00 = H[1][1] * H[2][2] - H[1][2] * H[1][2];
+        const double c01 = H[0][2] * H[1][2] - H[0][1] * H[2][2];
+        const double c02 = H[0][1] * H[1][2] - H[0][2] * H[1][1];
+        const double c11 = H[0][0] * H[2][2] - H[0][2] * H[0][2];
+        const double c12 = H[0][1] * H[0][2] - H[0][0] * H[1][2];
+        const double c22 = H[0][0] * H[1][1] - H[0][1] * H[0][1];
+        const double det = H[0][0] * c00 + H[0][1] * c01 + H[0][2] * c02;
+        if (fabs(det) < 1e-30) break;
+        double t[3];
+        t[0] = -(c00 * g[0] + c01 * g[1] + c02 * g[2]) / det;
+        t[1] = -(c01 * g[0] + c11 * g[1] + c12 * g[2]) / det;
+        t[2] = -(c02 * g[0] + c12 * g[1] + c22 * g[2]) / det;
+        const double lim = 0.5 + 0.01 * m;
+        if (fabs(t[0]) <= lim && fabs(t[1]) <= lim && fabs(t[2]) <= lim) {
+          conv = 1;
+          for (int d = 0; d < 3; ++d) o[d] = t[d];
+          value = v + 0.5 * (g[0] * t[0] + g[1] * t[1] + g[2] * t[2]);
+          break;
+        }
+        if (m == 10) break;
+        for (int d = 0; d < 3; ++d)
+          if (fabs(t[d]) > lim) p[d] += t[d] > 0.0 ? 1 : -1;
+      }
+      if (!conv) {
+        for (int d = 0; d < 3; ++d) p[d] = p0[d];
+        value = (double)D[lin];
+      }
+    }
+    bs_dog_pt r;
+    double f[3];
+    int i0[3], i1[3];
+    for (int d = 0; d < 3; ++d) {
+      r.loc[d] = (double)p[d] + o[d];
+      const double fl = floor(r.loc[d]);
+      f[d] = r.loc[d] - fl;
+      i0[d] = min(max((int)fl, 0), dims[d] - 1);
+      i1[d] = min(max((int)fl + 1, 0), dims[d] - 1);
+    }
+    double acc = 0.0;
+    for (int c = 0; c < 8; ++c) {
+      const int ix = (c & 1) ? i1[0] : i0[0], iy = (c & 2) ? i1[1] : i0[1],
+                iz = (c & 4) ? i1[2] : i0[2];
+      const double wx = (c & 1) ? f[0] : 1.0 - f[0],
+                   wy = (c & 2) ? f[1] : 1.0 - f[1],
+                   wz = (c & 4) ? f[2] : 1.0 - f[2];
+      acc += wx * wy * wz *
+             (double)dog_cvt(raw[(long)iz * plane + (long)iy * nx + ix]);
+    }
+    r.fin = (long long)p[2] * plane + (long long)p[1] * nx + p[0];
+    r.start = lin;
+    r.value = (float)value;
+    r.intensity = (float)acc;
+    r.kind = (code & 1) ? -1 : 1;
+    r.converged = conv;
+    r.keep = fabs(value) >= threshold ? 1 : 0;
+    r._pad = 0;
+    out[i] = r;
+  }
+}
+
+/* [PIN-SIGMA] + [PIN-GAUSS]: taps of one sigma, centred at DOG_WPAD + Rc */
+static int dog_taps(double s, int Rc, float *w) {
+  const int h = std::max(2, (int)(3.0 * s + 0.5) + 1), R = h - 1;
+  if (w) {
+    double sum = 0.0;
+    for (int x = -R; x <= R; ++x) sum += std::exp(-(double)x * x / (2.0 * s * s));
+    for (int x = -R; x <= R; ++x)
+      w[DOG_WPAD + Rc + x] =
+          (float)(std::exp(-(double)x * x / (2.0 * s * s)) / sum);
+  }
+  return R;
+}
+
+struct bs_dog_plan {
+  const bs_view_rec *view;
+  int nx, ny, nz;  /* detection-scale dims */
+  int R;           /* radius of the wider (sigma2) filter */
+  float wgt;
+  bs_dog_w w;
+  bool boxed;      /* ds != {1,1,1}: raw detection-scale input is dog_box */
+};
+
+static int dog_validate(bs_ctx *c, int32_t view_id, const bs_dog_params *p,
+                        bs_dog_plan *pl) {
+  auto it = c->views.find(view_id);
+  if (it == c->views.end()) return BS_ENOVIEW;
+  if (!(p->sigma > 0.5) || p->max_intensity == p->min_intensity ||
+      (!p->find_min && !p->find_max) ||
+      (p->localization != 0 && p->localization != 1)) {
+    c->err = "detect_dog: bad sigma / intensity range / type / localization";
+    return BS_EINVAL;
+  }
+  for (int d = 0; d < 3; ++d)
+    if (!is_pow2(p->ds[d])) {
+      c->err = "detect_dog: ds factors must be powers of two >= 1";
+      return BS_EINVAL;
+    }
+  const double k = std::pow(2.0, 0.25);
+  const double s1 = std::sqrt(p->sigma * p->sigma - 0.25);
+  const double s2 = std::sqrt(p->sigma * k * p->sigma * k - 0.25);
+  const int R2 = dog_taps(s2, 0, nullptr);
+  if (R2 > DOG_RMAX) {
+    c->err = "detect_dog: filter radius > 32";
+    return BS_EUNSUP;
+  }
+  pl->view = &it->second;
+  pl->nx = (int)(it->second.dims[0] / p->ds[0]);
+  pl->ny = (int)(it->second.dims[1] / p->ds[1]);
+  pl->nz = (int)(it->second.dims[2] / p->ds[2]);
+  if (pl->nx < 3 || pl->ny < 3 || pl->nz < 3) {
+    c->err = "detect_dog: detection-scale dims must be >= 3";
+    return BS_EUNSUP;
+  }
+  std::memset(&pl->w, 0, sizeof(pl->w));
+  pl->R = R2;
+  const int R1 = dog_taps(s1, R2, pl->w.w1);
+  (void)R1;
+  dog_taps(s2, R2, pl->w.w2);
+  pl->wgt = (float)(1.0 / (k - 1.0));
+  pl->boxed = p->ds[0] != 1 || p->ds[1] != 1 || p->ds[2] != 1;
+  return BS_OK;
+}
+
+/* box mean (if any) + both blur kernels: leaves D in c->dog_d */
+static int dog_volume(bs_ctx *c, const bs_dog_params *p,
+                      const bs_dog_plan *pl) {
+  const int nx = pl->nx, ny = pl->ny, nz = pl->nz, R = pl->R;
+  const size_t nvox = (size_t)nx * ny * nz;
+  int rc;
+  if (pl->boxed &&
+      (rc = ensure_dev(c, (void **)&c->dog_box, &c->dog_box_cap, nvox * 4)))
+    return rc;
+  if ((rc = ensure_dev(c, (void **)&c->dog_g1, &c->dog_g1_cap, nvox * 4)) ||
+      (rc = ensure_dev(c, (void **)&c->dog_g2, &c->dog_g2_cap, nvox * 4)) ||
+      (rc = ensure_dev(c, (void **)&c->dog_d, &c->dog_d_cap, nvox * 4)))
+    return rc;
+  const float lo = (float)p->min_intensity;
+  const float inv = (float)(1.0 / (p->max_intensity - p->min_intensity));
+  const int Ra = (R + 3) & ~3;
+  const size_t lds_xy = (size_t)(DOG_TY + 2 * R) *
+                        (DOG_TX + 2 * Ra + 2 * DOG_TX) * sizeof(float);
+  const size_t lds_z = (size_t)2 * (2 * R + 1) * 256 * sizeof(float);
+  const long txy = (long)((nx + DOG_TX - 1) / DOG_TX) *
+                   ((ny + DOG_TY - 1) / DOG_TY) * nz;
+  const long tz = (long)((nx + 63) / 64) * ((ny + 3) / 4) *
+                  ((nz + DOG_ZC - 1) / DOG_ZC);
+  if (pl->boxed) {
+    bs_tim t(c, BS_K_DOG_XY);
+    hipLaunchKernelGGL(k_dog_box, dim3(std::min(65536L, (long)ny * nz)),
+                       dim3(256), 0, c->stream, pl->view->dptr, c->dog_box,
+                       (int)pl->view->dims[0], (int)pl->view->dims[1], nx, ny,
+                       nz, p->ds[0], p->ds[1], p->ds[2]);
+  }
+  {
+    bs_tim t(c, BS_K_DOG_XY);
+    if (pl->boxed)
+      hipLaunchKernelGGL(k_dog_xy<float>, dim3(std::min(1L << 20, txy)),
+                         dim3(256), lds_xy, c->stream,
+                         (const float *)c->dog_box, c->dog_g1, c->dog_g2, nx,
+                         ny, nz, lo, inv, R, pl->w);
+    else
+      hipLaunchKernelGGL(k_dog_xy<unsigned short>,
+                         dim3(std::min(1L << 20, txy)), dim3(256), lds_xy,
+                         c->stream, (const unsigned short *)pl->view->dptr,
+                         c->dog_g1, c->dog_g2, nx, ny, nz, lo, inv, R, pl->w);
+  }
+  {
+    bs_tim t(c, BS_K_DOG_Z);
+    hipLaunchKernelGGL(k_dog_z, dim3(std::min(1L << 20, tz)), dim3(256),
+                       lds_z, c->stream, c->dog_g1, c->dog_g2, c->dog_d, nx,
+                       ny, nz, R, pl->wgt, pl->w);
+  }
+  CHK(c, hipGetLastError());
+  return BS_OK;
+}
+
+/* the widest filter needs 96 KB (xy) / 130 KB (z) of dynamic LDS */
+static void dog_lds_optin() {
+  (void)hipFuncSetAttribute((const void *)k_dog_xy<float>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+  (void)hipFuncSetAttribute((const void *)k_dog_xy<unsigned short>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+  (void)hipFuncSetAttribute((const void *)k_dog_z,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+}
+
+extern "C" int bs_debug_dog_volume(bs_ctx *c, int32_t view_id,
+                                   const bs_dog_params *p, float *out,
+                                   int64_t out_dims[3]) {
+  if (!c || !p || !out_dims) return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  CHK(c, hipSetDevice(c->dev));
+  bs_dog_plan pl;
+  int rc = dog_validate(c, view_id, p, &pl);
+  if (rc) return rc;
+  out_dims[0] = pl.nx;
+  out_dims[1] = pl.ny;
+  out_dims[2] = pl.nz;
+  if (!out) return BS_OK;
+  dog_lds_optin();
+  if ((rc = dog_volume(c, p, &pl))) return rc;
+  CHK(c, hipMemcpyAsync(out, c->dog_d, (size_t)pl.nx * pl.ny * pl.nz * 4,
+                        hipMemcpyDeviceToHost, c->stream));
+  CHK(c, hipStreamSynchronize(c->stream));
+  flush_stats(c);
+  return BS_OK;
+}
+
+extern "C" int bs_detect_dog(bs_ctx *c, int32_t view_id,
+                             const bs_dog_params *p, bs_interest_point *out,
+                             size_t capacity, size_t *n_found) {
+  if (!c || !p || !n_found || (capacity > 0 && !out)) return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  CHK(c, hipSetDevice(c->dev));
+  bs_dog_plan pl;
+  int rc = dog_validate(c, view_id, p, &pl);
+  if (rc) return rc;
+  dog_lds_optin();
+  if ((rc = dog_volume(c, p, &pl))) return rc;
+  const int nx = pl.nx, ny = pl.ny, nz = pl.nz;
+  if ((rc = ensure_dev(c, (void **)&c->dog_cnt, &c->dog_cnt_cap, 4)) ||
+      (rc = ensure_dev(c, (void **)&c->dog_cand, &c->dog_cand_cap,
+                       c->dog_init_cap * sizeof(long long))))
+    return rc;
+  const float gate = (float)(p->localization == 1 ? p->threshold / 3.0
+                                                  : p->threshold);
+  const long erows = (long)(ny - 2) * (nz - 2);
+  unsigned int ncand = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const size_t cap = c->dog_cand_cap / sizeof(long long);
+    CHK(c, hipMemsetAsync(c->dog_cnt, 0, 4, c->stream));
+    {
+      bs_tim t(c, BS_K_DOG_EXTREMA);
+      hipLaunchKernelGGL(k_dog_extrema, dim3(std::min(65536L, erows)),
+                         dim3(256), 0, c->stream, c->dog_d, nx, ny, nz, gate,
+                         p->find_min, p->find_max, c->dog_cand,
+                         (unsigned int)std::min(cap, (size_t)0xFFFFFFFFu),
+                         c->dog_cnt);
+    }
+    CHK(c, hipMemcpyAsync(&ncand, c->dog_cnt, 4, hipMemcpyDeviceToHost,
+                          c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (ncand <= cap) break;
+    if (pass == 1) {
+      c->err = "detect_dog: candidate count changed between scans";
+      return BS_EHIP;
+    }
+    /* overflow: grow to the exact count and rerun the scan only */
+    if ((rc = ensure_dev(c, (void **)&c->dog_cand, &c->dog_cand_cap,
+                         (size_t)ncand * sizeof(long long))))
+      return rc;
+  }
+  std::vector<bs_dog_pt> pts(ncand);
+  if (ncand) {
+    if ((rc = ensure_dev(c, (void **)&c->dog_pts, &c->dog_pts_cap,
+                         (size_t)ncand * sizeof(bs_dog_pt))))
+      return rc;
+    const unsigned int blocks = std::min(4096u, (ncand + 255u) / 256u);
+    {
+      bs_tim t(c, BS_K_DOG_SUBPIX);
+      if (pl.boxed)
+        hipLaunchKernelGGL(k_dog_subpix<float>, dim3(blocks), dim3(256), 0,
+                           c->stream, c->dog_d, (const float *)c->dog_box, nx,
+                           ny, nz, c->dog_cand, ncand, p->localization,
+                           p->threshold, c->dog_pts);
+      else
+        hipLaunchKernelGGL(k_dog_subpix<unsigned short>, dim3(blocks),
+                           dim3(256), 0, c->stream, c->dog_d,
+                           (const unsigned short *)pl.view->dptr, nx, ny, nz,
+                           c->dog_cand, ncand, p->localization, p->threshold,
+                           c->dog_pts);
+    }
+    CHK(c, hipMemcpyAsync(pts.data(), c->dog_pts,
+                          (size_t)ncand * sizeof(bs_dog_pt),
+                          hipMemcpyDeviceToHost, c->stream));
+  }
+  CHK(c, hipStreamSynchronize(c->stream));
+  flush_stats(c);
+  pts.erase(std::remove_if(pts.begin(), pts.end(),
+                           [](const bs_dog_pt &a) { return !a.keep; }),
+            pts.end());
+  std::sort(pts.begin(), pts.end(), [](const bs_dog_pt &a, const bs_dog_pt &b) {
+    if (a.fin != b.fin) return a.fin < b.fin;
+    if (a.kind != b.kind) return a.kind > b.kind;
+    return a.start < b.start;
+  });
+  *n_found = pts.size();
+  const size_t nw = std::min(pts.size(), capacity);
+  for (size_t i = 0; i < nw; ++i) {
+    for (int d = 0; d < 3; ++d) /* [PIN-MIP] detection scale -> view px */
+      out[i].loc[d] = p->ds[d] * pts[i].loc[d] + (p->ds[d] - 1) * 0.5;
+    out[i].value = pts[i].value;
+    out[i].intensity = pts[i].intensity;
+    out[i].kind = pts[i].kind;
+    out[i].converged = pts[i].converged;
+  }
   return BS_OK;
 }

@@ -251,6 +251,57 @@ void SpimData::set_stitching_results(
   }
 }
 
+std::string SpimData::interest_point_group(int tp, int setup,
+                                           const std::string &label) {
+  return "tpId_" + std::to_string(tp) + "_viewSetupId_" +
+         std::to_string(setup) + "/" + label;
+}
+
+std::vector<InterestPointEntry> SpimData::interest_points() const {
+  std::vector<InterestPointEntry> out;
+  auto vip = root->child("ViewInterestPoints");
+  if (!vip) return out;
+  for (auto &f : vip->all("ViewInterestPointsFile")) {
+    InterestPointEntry e;
+    auto attr = [&](const char *k) {
+      auto it = f->attrs.find(k);
+      return it == f->attrs.end() ? std::string() : it->second;
+    };
+    e.timepoint = atoi(attr("timepoint").c_str());
+    e.setup = atoi(attr("setup").c_str());
+    e.label = attr("label");
+    e.params = attr("params");
+    e.path = f->text;
+    out.push_back(e);
+  }
+  return out;
+}
+
+void SpimData::set_interest_points(const InterestPointEntry &e) {
+  auto vip = root->child("ViewInterestPoints");
+  if (!vip) vip = root->add("ViewInterestPoints");
+  const std::string tp = std::to_string(e.timepoint),
+                    su = std::to_string(e.setup);
+  auto &ch = vip->children;
+  ch.erase(std::remove_if(ch.begin(), ch.end(),
+                          [&](const bsx::NodePtr &c) {
+                            auto a = [&](const char *k) {
+                              auto it = c->attrs.find(k);
+                              return it == c->attrs.end() ? std::string()
+                                                          : it->second;
+                            };
+                            return c->tag == "ViewInterestPointsFile" &&
+                                   a("timepoint") == tp && a("setup") == su &&
+                                   a("label") == e.label;
+                          }),
+           ch.end());
+  auto f = vip->add_text("ViewInterestPointsFile", e.path);
+  f->attrs["timepoint"] = tp;
+  f->attrs["setup"] = su;
+  f->attrs["label"] = e.label;
+  f->attrs["params"] = e.params;
+}
+
 namespace {
 /* "0,1,2" -> set; empty string -> nullopt-like empty set + false */
 bool parse_idlist(const std::string &s, std::vector<int> *out) {

@@ -49,6 +49,17 @@ struct StitchEntry {
   double r = 0, hash = 0;
 };
 
+/* One <ViewInterestPointsFile> entry [PIN-IPXML]: restates mvrecon's
+ * XmlIoViewInterestPoints serialization (artifact un-vendored) —
+ *   <ViewInterestPoints>
+ *     <ViewInterestPointsFile timepoint="T" setup="S" label="L"
+ *         params="...">tpId_T_viewSetupId_S/L</ViewInterestPointsFile>
+ * with the element text being the group inside interestpoints.n5. */
+struct InterestPointEntry {
+  int timepoint = 0, setup = 0;
+  std::string label, params, path;
+};
+
 struct SpimData {
   std::string xml_path, base_dir;
   bsx::NodePtr root;
@@ -70,6 +81,14 @@ struct SpimData {
 
   std::vector<StitchEntry> stitching_results() const;
   void set_stitching_results(const std::vector<StitchEntry> &entries);
+
+  /* <ViewInterestPoints> accessors. set_interest_points adds the section
+   * under the root if absent and replaces an existing entry of the same
+   * (timepoint, setup, label); entries of other labels are kept. */
+  std::vector<InterestPointEntry> interest_points() const;
+  void set_interest_points(const InterestPointEntry &e);
+  static std::string interest_point_group(int tp, int setup,
+                                          const std::string &label);
 
   static double calculate_hash(const std::array<double, 12> &a,
                                const std::array<double, 12> &b);

@@ -265,6 +265,74 @@ int bs_debug_peak_scan(bs_ctx *ctx, const float *pcm_host,
                        const int64_t dims[3], int mode, float v[5],
                        int64_t idx[5], int *fell_back);
 
+/* -------------------------------------------- interest point detection */
+
+/* Difference-of-Gaussian interest point detection on one uploaded view.
+ * Replaces the in-process call site
+ *   net.preibisch.mvrecon.process.interestpointdetection.methods.dog
+ *       .DoGImgLib2.computeDoG(input, mask, sigma, threshold, localization,
+ *           findMin, findMax, minIntensity, maxIntensity, blockSize, service,
+ *           cuda = null, deviceCUDA = null, accurateCUDA, percentGPUMem)
+ *     -> ArrayList<InterestPoint>
+ * called from reference SparkInterestPointDetection.java:552-568. DoGImgLib2
+ * is not part of the reference tree, so the arithmetic is this project's
+ * restatement of the published method (Lowe 2004; Preibisch 2010), pinned by
+ * tests/dog_ref.py; each restated constant carries a [PIN-*] tag:
+ *   [PIN-DS2X]   residual downsample = float box mean over ds cells,
+ *                output dims floor(n/ds) (trailing partial cell dropped)
+ *   [PIN-SIGMA]  k = 2^(1/4), sigma2 = sigma*k, image sigma 0.5,
+ *                s_i = sqrt(sigma_i^2 - 0.25), weight 1/(k-1)
+ *   [PIN-GAUSS]  half size h = max(2, (int)(3 s + 0.5) + 1), taps
+ *                exp(-x^2 / 2 s^2) over |x| <= h-1 normalised to unit sum,
+ *                separable, mirror boundary with the edge sample repeated
+ *   [PIN-DOG-SIGN] D = (G_s1 - G_s2) * weight: bright blob = positive maximum
+ *   [PIN-EXTREMA] strict 26-neighbour extrema, all neighbours inside
+ *   [PIN-THRESH] gate |D| >= threshold (NONE) or threshold/3 (QUADRATIC),
+ *                then |fitted value| >= threshold
+ *   [PIN-SUBPIX] iterative quadratic fit, at most 10 moves, accept when
+ *                every |offset| <= 0.5 + 0.01*move
+ * All arithmetic is float32 on the device except the per-candidate 3x3
+ * solve, which is double. */
+typedef struct {
+  double sigma, threshold, min_intensity, max_intensity;
+  int32_t find_min, find_max; /* --type MIN / MAX / BOTH */
+  int32_t localization;       /* 0 NONE, 1 QUADRATIC */
+  int32_t ds[3];              /* residual box-mean factors, powers of 2 */
+} bs_dog_params;
+
+typedef struct {
+  double loc[3];     /* x,y,z in uploaded-view pixels: f*x + (f-1)/2 per
+                        axis with residual factor f ([PIN-MIP]) */
+  float value;       /* (fitted) DoG value */
+  float intensity;   /* raw detection-scale input, trilinear at loc,
+                        border clamped (reference :586-601) */
+  int32_t kind;      /* +1 maximum, -1 minimum */
+  int32_t converged; /* QUADRATIC: 1 if the fit was accepted, 0 if the point
+                        is reported at its integer voxel; NONE: always 1 */
+} bs_interest_point;
+
+/* Detect on view_id. Writes min(*n_found, capacity) points — the first ones
+ * in the order below — and always sets *n_found to the full count (out may
+ * be NULL when capacity == 0; call twice to size the buffer). Points are
+ * sorted by the linear index of their final integer voxel, maxima before
+ * minima on a tie, then by the voxel they started from; the same arguments
+ * give bit-identical arrays on every call.
+ * Errors: BS_ENOVIEW unknown view; BS_EINVAL sigma <= 0.5, max_intensity ==
+ * min_intensity, a ds factor that is not a power of two >= 1, neither
+ * find_min nor find_max, localization not 0/1; BS_EUNSUP filter radius
+ * h-1 > 32 or a detection-scale dim < 3; BS_ENOMEM when the float
+ * temporaries (12 B/voxel, +4 with ds != 1) do not fit — the whole view is
+ * processed at once. */
+int bs_detect_dog(bs_ctx *ctx, int32_t view_id, const bs_dog_params *params,
+                  bs_interest_point *out, size_t capacity, size_t *n_found);
+
+/* Debug-only (parity tooling): the DoG volume D at detection scale, x
+ * fastest. out_dims receives {nx,ny,nz} = floor(view dims / ds); with
+ * out == NULL only the dims are returned. */
+int bs_debug_dog_volume(bs_ctx *ctx, int32_t view_id,
+                        const bs_dog_params *params, float *out,
+                        int64_t out_dims[3]);
+
 /* ------------------------------------------------------- instrumentation */
 
 /* Per-kernel timing, HIP-event measured on the launch stream (bench.py
@@ -287,6 +355,11 @@ enum bs_kernel_id {
   BS_K_PYRAMID,    /* 2x (or general) box-mean pyramid level */
   BS_K_PEAK_ROWS,  /* peak prefilter chain (row maxima -> top five);
                       BS_K_PEAK/_MERGE then count only fallback scans */
+  BS_K_DOG_XY,      /* fused x+y Gaussian passes, both sigmas (also counts
+                       the residual box-mean launch when ds != 1) */
+  BS_K_DOG_Z,       /* z pass for both sigmas + subtract + scale -> D */
+  BS_K_DOG_EXTREMA, /* 3x3x3 strict extremum scan + gate + compaction */
+  BS_K_DOG_SUBPIX,  /* per-candidate quadratic fit + intensity sample */
   BS_K_COUNT
 };
 
