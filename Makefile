@@ -8,7 +8,7 @@ LIB = bigstitcher_spark_amd/libbigstitch.so
 
 all: $(LIB) cli
 
-$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip include/bigstitch.h
+$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h include/bigstitch.h
 	$(HIPCC) $(CXXFLAGS) -shared -Iinclude $< -o $@
 
 resource-report: bigstitcher_spark_amd/csrc/bigstitch.hip

@@ -165,6 +165,8 @@ def load_lib():
     lib.bs_debug_peak_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3,
                                        C.c_int, C.c_float * 5, C.c_int64 * 5,
                                        C.POINTER(C.c_int)]
+    lib.bs_debug_rtest.argtypes = [C.c_void_p, C.POINTER(_Pair), C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_void_p]
     lib.bs_detect_dog.argtypes = [C.c_void_p, C.c_int32,
                                   C.POINTER(_DogParams), C.c_void_p,
                                   C.c_size_t, C.POINTER(C.c_size_t)]
@@ -471,6 +473,32 @@ class Context:
         )
         return (np.array(v[:], np.float32), np.array(idx[:], np.int64),
                 bool(fb.value))
+
+    def debug_rtest(self, pair, shifts):
+        """Run this context's r-test kernel (BS_CORR_MODE) on integer
+        shifts (n, 3) = (sx, sy, sz) of one pair dict at ds = 1, without
+        the min_overlap filter. Returns (sums uint64 (n, 5) = sum a, b, aa,
+        bb, ab over each overlap, voxel counts int64 (n,))."""
+        cp = _Pair()
+        cp.view_a = pair["view_a"]
+        cp.view_b = pair["view_b"]
+        for d in range(3):
+            cp.off_a[d] = pair["off_a"][d]
+            cp.size_a[d] = pair["size_a"][d]
+            cp.off_b[d] = pair["off_b"][d]
+            cp.size_b[d] = pair["size_b"][d]
+        sh = np.ascontiguousarray(shifts, np.int32).reshape(-1, 3)
+        n = len(sh)
+        sums = np.zeros((n, 5), np.uint64)
+        nvox = np.zeros(n, np.int64)
+        self._check(
+            self._lib.bs_debug_rtest(
+                self._h, C.byref(cp), sh.ctypes.data_as(C.c_void_p), n,
+                sums.ctypes.data_as(C.c_void_p),
+                nvox.ctypes.data_as(C.c_void_p)),
+            "bs_debug_rtest",
+        )
+        return sums, nvox
 
     # -- stats ------------------------------------------------------------
     def stats(self):

@@ -35,6 +35,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rtest_walk.h"
+
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1729,10 +1731,9 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
  * sums are order-independent -> bit-exact [PIN-R]. The per-candidate
  * row walk uses the adaptive row width (rows here are single y-lines,
  * no division anywhere). */
-template <bool R4>
-__device__ __forceinline__ void rtest_body(bs_region a, bs_region b,
-                                           const bs_cand *cands,
-                                           int nc, u64 *sums) {
+__global__ __launch_bounds__(256) void k_rtest(bs_region a, bs_region b,
+                                               const bs_cand *cands,
+                                               int nc, u64 *sums) {
   __shared__ u64 ws[4][5];
   const int tid = threadIdx.x;
   const int z = blockIdx.x;
@@ -1794,38 +1795,6 @@ __device__ __forceinline__ void rtest_body(bs_region a, bs_region b,
         }
       };
       int r = r00;
-      if (R4) /* 4 rows in flight: deeper MLP for the latency-bound
-                 dual-stream scan; u64 sums keep it bit-exact [PIN-R] */
-        for (; r + 3 * rstride < c.ny; r += 4 * rstride) {
-          if (h && lx == 0)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              add1(ar[q * astep], br[q * bstep]);
-          if (tail && lx == rw - 1)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              add1(ar[q * astep + c.nx - 1], br[q * bstep + c.nx - 1]);
-          for (int p = lx; p < np2; p += rw) {
-            unsigned av[4], bv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              av[q] = ((const unsigned *)(ar + q * astep + h))[p];
-              bv[q] = ((const unsigned *)(br + q * bstep + h))[p];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const unsigned al = av[q] & 0xFFFFu, ah = av[q] >> 16;
-              const unsigned bl = bv[q] & 0xFFFFu, bh = bv[q] >> 16;
-              pa += al + ah;
-              pb += bl + bh;
-              paa += (u64)(al * al) + (u64)(ah * ah);
-              pbb += (u64)(bl * bl) + (u64)(bh * bh);
-              pab += (u64)(al * bl) + (u64)(ah * bh);
-            }
-          }
-          ar += 4 * astep;
-          br += 4 * bstep;
-        }
       for (; r + rstride < c.ny; r += 2 * rstride) {
         if (h && lx == 0) {
           add1(ar[0], br[0]);
@@ -1896,17 +1865,79 @@ __device__ __forceinline__ void rtest_body(bs_region a, bs_region b,
   }
 }
 
-__global__ __launch_bounds__(256) void k_rtest(bs_region a, bs_region b,
-                                               const bs_cand *cands,
-                                               int nc, u64 *sums) {
-  rtest_body<false>(a, b, cands, nc, sums);
-}
-
-/* 4-rows-in-flight A/B (BS_CORR_R4) */
-__global__ __launch_bounds__(256) void k_rtest_r4(bs_region a, bs_region b,
-                                                  const bs_cand *cands,
-                                                  int nc, u64 *sums) {
-  rtest_body<true>(a, b, cands, nc, sums);
+/* Same plane-stationary scan (BS_CORR_MODE=wide, the default), row walk in
+ * 16-byte chunks for every shift parity: a lane owns one aligned chunk of
+ * the A row and cuts its 8 B partners out of two aligned B chunks (see
+ * rtest_walk.h for the arithmetic and the bounds argument). Lanes per row
+ * are a power of two covering the row's chunks, at most one wave; longer
+ * rows loop. ROWS rows are fetched before any is consumed (3 measured best
+ * in the pipelined benchmark). The sums are the same
+ * integers in another order -> bit-identical to k_rtest [PIN-R]. */
+__global__ __launch_bounds__(256) void k_rtest_wide(bs_region a, bs_region b,
+                                                    const bs_cand *cands,
+                                                    int nc, u64 *sums) {
+  constexpr int ROWS = 3;
+  __shared__ u64 ws[4][5];
+  const int tid = threadIdx.x;
+  const int z = blockIdx.x;
+  for (int ci = 0; ci < nc; ++ci) {
+    const bs_cand c = cands[ci];
+    if (z < c.loz || z >= c.loz + c.nz) continue; /* block-uniform */
+    const int nchmax = bs_rw_max_chunks(c.nx);
+    int rw = 1;
+    while (rw < nchmax && rw < 64) rw <<= 1;
+    const int rsh = __ffs(rw) - 1;
+    const int rpg = 256 >> rsh;
+    const int lx = tid & (rw - 1);
+    const int lr = tid >> rsh;
+    const int rstride = gridDim.y * rpg;
+    int r = blockIdx.y * rpg + lr;
+    long ea = (a.oz + z) * a.sxy + (a.oy + c.loy + r) * a.sx + a.ox + c.lox;
+    long eb = (b.oz + z + c.sz) * b.sxy + (b.oy + c.loy + c.sy + r) * b.sx +
+              b.ox + c.lox + c.sx;
+    const long astep = (long)rstride * a.sx, bstep = (long)rstride * b.sx;
+    uint64_t s[5] = {0, 0, 0, 0, 0};
+    for (; r + (ROWS - 1) * rstride < c.ny; r += ROWS * rstride) {
+      bs_rw_row rr[ROWS];
+      int nch = 0;
+#pragma unroll
+      for (int q = 0; q < ROWS; ++q) {
+        rr[q] = bs_rw_setup(ea + q * astep, eb + q * bstep, c.nx);
+        nch = max(nch, rr[q].nch);
+      }
+      for (int k = lx; k < nch; k += rw) {
+        bs_rw_step st[ROWS];
+#pragma unroll
+        for (int q = 0; q < ROWS; ++q)
+          st[q] = bs_rw_fetch(a.ptr, b.ptr, rr[q], k);
+#pragma unroll
+        for (int q = 0; q < ROWS; ++q) bs_rw_consume(st[q], rr[q].de, s);
+      }
+      ea += ROWS * astep;
+      eb += ROWS * bstep;
+    }
+    for (; r < c.ny; r += rstride) {
+      const bs_rw_row r0 = bs_rw_setup(ea, eb, c.nx);
+      for (int k = lx; k < r0.nch; k += rw)
+        bs_rw_consume(bs_rw_fetch(a.ptr, b.ptr, r0, k), r0.de, s);
+      ea += astep;
+      eb += bstep;
+    }
+    u64 pa = wave_sum_u64(s[0]), pb = wave_sum_u64(s[1]),
+        paa = wave_sum_u64(s[2]), pbb = wave_sum_u64(s[3]),
+        pab = wave_sum_u64(s[4]);
+    int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) {
+      ws[wave][0] = pa; ws[wave][1] = pb; ws[wave][2] = paa;
+      ws[wave][3] = pbb; ws[wave][4] = pab;
+    }
+    __syncthreads();
+    if (tid < 5) {
+      u64 sv = ws[0][tid] + ws[1][tid] + ws[2][tid] + ws[3][tid];
+      atomicAdd(&sums[(long)ci * 5 + tid], sv);
+    }
+    __syncthreads(); /* ws reused next candidate */
+  }
 }
 
 /* ---------------------------------------------------------------- fusion */
@@ -2446,6 +2477,7 @@ struct bs_ctx {
   size_t dvol_cap = 0;
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   int peak_full = 0; /* BS_PEAK_MODE=full: always the full peak scan */
+  int corr_wide = 1; /* BS_CORR_MODE=wide (default) | legacy r-test */
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
   bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
   long dbg_px = 0, dbg_py = 0, dbg_pz = 0;
@@ -2483,6 +2515,13 @@ extern "C" const char *bs_last_error(const bs_ctx *ctx) {
   return ctx ? ctx->err.c_str() : g_err.c_str();
 }
 
+/* uint16 volumes the r-test reads are sized to whole 16-byte chunks, so
+ * an aligned 16-byte load that starts inside one ends inside it
+ * (rtest_walk.h) */
+static size_t rtest_alloc_bytes(size_t bytes) {
+  return (bytes + 15) & ~(size_t)15;
+}
+
 static int ensure_dev(bs_ctx *c, void **p, size_t *cap, size_t need) {
   if (need <= *cap) return BS_OK;
   if (*p) (void)hipFree(*p);
@@ -2513,6 +2552,8 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   }
   if (const char *e = getenv("BS_PEAK_MODE")) /* auto (default) | full */
     c->peak_full = strcmp(e, "full") == 0;
+  if (const char *e = getenv("BS_CORR_MODE")) /* wide (default) | legacy */
+    c->corr_wide = strcmp(e, "legacy") != 0;
   if (const char *e = getenv("BS_DOG_INIT_CAP")) {
     long v = atol(e);
     if (v >= 1) c->dog_init_cap = (size_t)v;
@@ -2724,7 +2765,7 @@ extern "C" int bs_view_upload(bs_ctx *c, int32_t id, const uint16_t *data,
     c->views.erase(it);
   }
   unsigned short *d;
-  CHK(c, hipMalloc(&d, n * 2));
+  CHK(c, hipMalloc(&d, rtest_alloc_bytes(n * 2)));
   CHK(c, hipMemcpy(d, data, n * 2, hipMemcpyHostToDevice));
   c->views[id] = {d, {dims[0], dims[1], dims[2]}};
   return BS_OK;
@@ -2799,7 +2840,7 @@ extern "C" int bs_view_synth(bs_ctx *c, int32_t id, const int64_t dims[3],
     c->views.erase(it);
   }
   unsigned short *d;
-  CHK(c, hipMalloc(&d, n * 2));
+  CHK(c, hipMalloc(&d, rtest_alloc_bytes(n * 2)));
   CHK(c, hipMemsetAsync(c->synth_acc, 0, n * 8, c->stream));
   if (n_blobs > 0) {
     CHK(c, hipMemcpyAsync(c->dblobs, blobs, (size_t)n_blobs * 5 * 4,
@@ -2844,7 +2885,7 @@ extern "C" int bs_view_combine_avg(bs_ctx *c, int32_t out_id,
   }
   size_t nvox = (size_t)dims[0] * dims[1] * dims[2];
   unsigned short *dout;
-  CHK(c, hipMalloc(&dout, nvox * 2));
+  CHK(c, hipMalloc(&dout, rtest_alloc_bytes(nvox * 2)));
   {
     long blocks = std::min((long)4096, (long)((nvox + 255) / 256));
     hipLaunchKernelGGL(k_view_avg, dim3(blocks), dim3(256), 0, c->stream,
@@ -3071,7 +3112,8 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
                     off[0], off[1], off[2],
                     sl->m[t][0], sl->m[t][1], sl->m[t][2]};
     } else {
-      size_t need = (size_t)sl->m[t][0] * sl->m[t][1] * sl->m[t][2] * 2;
+      size_t need = rtest_alloc_bytes((size_t)sl->m[t][0] * sl->m[t][1] *
+                                      sl->m[t][2] * 2);
       int rc = ensure_dev(c, (void **)&sl->regbuf[t], &sl->reg_cap[t], need);
       if (rc) return rc;
       bs_region src = {vr.dptr, vr.dims[0], vr.dims[0] * vr.dims[1],
@@ -3291,6 +3333,61 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
   return BS_OK;
 }
 
+/* Overlap box of A (dims ma) and B (dims mb) under the integer shift s, in
+ * A coordinates [PIN-R]; fills h->gc and h->n. False when it is empty. */
+static bool cand_box(const int ma[3], const int mb[3], const int s[3],
+                     bs_hostcand *h) {
+  int lo[3], hi[3];
+  for (int d = 0; d < 3; ++d) {
+    lo[d] = std::max(0, -s[d]);
+    hi[d] = std::min(ma[d], mb[d] - s[d]);
+    if (hi[d] <= lo[d]) return false;
+  }
+  h->gc = {lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1],
+           hi[2] - lo[2], s[0], s[1], s[2]};
+  h->n = (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+  return true;
+}
+
+/* Sort sl->hc (non-empty) by z-shift, upload it, and launch the context's
+ * r-test over sl->reg[0..1] on the slot's stream, followed by the copy of
+ * the raw sums to sl->hsums (index-aligned with the sorted hc). */
+static int rtest_issue(bs_ctx *c, bs_slot *sl) {
+  /* group candidates sharing a z-shift so the plane-stationary
+   * r-test's B-plane reads repeat consecutively (L2 hits); u64 sums
+   * are order-independent and hc/gc stay index-aligned, so results
+   * are unchanged */
+  std::stable_sort(sl->hc.begin(), sl->hc.end(),
+                   [](const bs_hostcand &x, const bs_hostcand &y) {
+                     return x.gc.sz < y.gc.sz;
+                   });
+  std::vector<bs_cand> gc(sl->hc.size());
+  for (size_t i = 0; i < sl->hc.size(); ++i) gc[i] = sl->hc[i].gc;
+  CHK(c, hipMemcpyAsync(sl->dcands, gc.data(), gc.size() * sizeof(bs_cand),
+                        hipMemcpyHostToDevice, sl->stream));
+  CHK(c, hipMemsetAsync(sl->dsums, 0, gc.size() * 5 * sizeof(u64),
+                        sl->stream));
+  CHK(c, hipStreamSynchronize(sl->stream)); /* gc dies at scope end */
+  {
+    int maxz = 1;
+    for (auto &h : sl->hc)
+      maxz = std::max(maxz, h.gc.loz + h.gc.nz);
+    bs_tim tt(c, BS_K_CORR, sl->stream);
+    static const int corr_gy = [] {
+      const char *e = getenv("BS_CORR_GY");
+      return e ? atoi(e) : 8; /* measured: 8 > 4 > 2 >> 1 at 512^3 */
+    }();
+    hipLaunchKernelGGL(c->corr_wide ? k_rtest_wide : k_rtest,
+                       dim3((unsigned)maxz, corr_gy), dim3(256),
+                       0, sl->stream, sl->reg[0], sl->reg[1], sl->dcands,
+                       (int)gc.size(), sl->dsums);
+  }
+  CHK(c, hipMemcpyAsync(sl->hsums, sl->dsums,
+                        sl->hc.size() * 5 * sizeof(u64),
+                        hipMemcpyDeviceToHost, sl->stream));
+  return BS_OK;
+}
+
 /* Phase B: wait for the top-5, build the periodic candidate set
  * [PIN-CAND], launch r-test + sub-pixel gather; records sl->done. */
 static int stitch_phaseB(bs_ctx *c, bs_slot *sl,
@@ -3326,59 +3423,17 @@ static int stitch_phaseB(bs_ctx *c, bs_slot *sl,
       if (ci & 1) sxyz[0] -= sl->Px;
       if (ci & 2) sxyz[1] -= sl->Py;
       if (ci & 4) sxyz[2] -= sl->Pz;
-      int lo[3], hi[3];
-      bool ok = true;
-      for (int d = 0; d < 3; ++d) {
-        lo[d] = std::max(0, -sxyz[d]);
-        hi[d] = std::min(sl->m[0][d], sl->m[1][d] - sxyz[d]);
-        if (hi[d] <= lo[d]) ok = false;
-      }
-      if (!ok) continue;
-      long n = (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
-      if ((double)n < std::max(min_n, 1.0)) continue;
       bs_hostcand h;
-      h.gc = {lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1],
-              hi[2] - lo[2], sxyz[0], sxyz[1], sxyz[2]};
+      if (!cand_box(sl->m[0], sl->m[1], sxyz, &h)) continue;
+      if ((double)h.n < std::max(min_n, 1.0)) continue;
       h.rank = k;
       h.ci = ci;
-      h.n = n;
       sl->hc.push_back(h);
     }
   }
   if (!sl->hc.empty()) {
-    /* group candidates sharing a z-shift so the plane-stationary
-     * r-test's B-plane reads repeat consecutively (L2 hits); u64 sums
-     * are order-independent and hc/gc stay index-aligned, so results
-     * are unchanged */
-    std::stable_sort(sl->hc.begin(), sl->hc.end(),
-                     [](const bs_hostcand &x, const bs_hostcand &y) {
-                       return x.gc.sz < y.gc.sz;
-                     });
-    std::vector<bs_cand> gc(sl->hc.size());
-    for (size_t i = 0; i < sl->hc.size(); ++i) gc[i] = sl->hc[i].gc;
-    CHK(c, hipMemcpyAsync(sl->dcands, gc.data(), gc.size() * sizeof(bs_cand),
-                          hipMemcpyHostToDevice, sl->stream));
-    CHK(c, hipMemsetAsync(sl->dsums, 0, gc.size() * 5 * sizeof(u64),
-                          sl->stream));
-    CHK(c, hipStreamSynchronize(sl->stream)); /* gc dies at scope end */
-    {
-      int maxz = 1;
-      for (auto &h : sl->hc)
-        maxz = std::max(maxz, h.gc.loz + h.gc.nz);
-      bs_tim tt(c, BS_K_CORR, sl->stream);
-      static const int corr_gy = [] {
-        const char *e = getenv("BS_CORR_GY");
-        return e ? atoi(e) : 8; /* measured: 8 > 4 > 2 >> 1 at 512^3 */
-      }();
-      static const bool corr_r4 = getenv("BS_CORR_R4") != nullptr;
-      hipLaunchKernelGGL(corr_r4 ? k_rtest_r4 : k_rtest,
-                         dim3((unsigned)maxz, corr_gy), dim3(256),
-                         0, sl->stream, sl->reg[0], sl->reg[1], sl->dcands,
-                         (int)gc.size(), sl->dsums);
-    }
-    CHK(c, hipMemcpyAsync(sl->hsums, sl->dsums,
-                          sl->hc.size() * 5 * sizeof(u64),
-                          hipMemcpyDeviceToHost, sl->stream));
+    rc = rtest_issue(c, sl);
+    if (rc) return rc;
     CHK(c, hipMemcpyAsync(sl->dpkidx, pkidx, sl->npk * sizeof(long long),
                           hipMemcpyHostToDevice, sl->stream));
     {
@@ -3560,6 +3615,63 @@ extern "C" int bs_debug_peak_scan(bs_ctx *c, const float *pcm_host,
     v[k] = sl->htop5[k].v;
     idx[k] = sl->htop5[k].idx;
   }
+  return BS_OK;
+}
+
+/* Debug-only: the context's r-test (BS_CORR_MODE) on caller-chosen
+ * integer shifts of one pair at ds = 1: boxes from cand_box, launch
+ * through rtest_issue exactly as phase B, no min_overlap filter. Uses
+ * slot 0; call between batches. */
+extern "C" int bs_debug_rtest(bs_ctx *c, const bs_pair_desc *pd,
+                              const int32_t (*shifts)[3], int n,
+                              uint64_t (*sums_out)[5], int64_t *nvox_out) {
+  if (!c || !pd || !shifts || !sums_out || !nvox_out || n < 1 || n > 64)
+    return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  CHK(c, hipSetDevice(c->dev));
+  bs_slot *sl = &c->slot[0];
+  auto ita = c->views.find(pd->view_a);
+  auto itb = c->views.find(pd->view_b);
+  if (ita == c->views.end() || itb == c->views.end()) {
+    c->err = "view not uploaded";
+    return BS_ENOVIEW;
+  }
+  for (int t = 0; t < 2; ++t) {
+    const bs_view_rec &vr = t == 0 ? ita->second : itb->second;
+    const int64_t *off = t == 0 ? pd->off_a : pd->off_b;
+    const int64_t *size = t == 0 ? pd->size_a : pd->size_b;
+    for (int d = 0; d < 3; ++d) {
+      if (off[d] < 0 || size[d] <= 0 || off[d] + size[d] > vr.dims[d]) {
+        c->err = "pair interval out of view bounds";
+        return BS_EINVAL;
+      }
+      sl->m[t][d] = (int)size[d];
+    }
+    sl->reg[t] = {vr.dptr, vr.dims[0], vr.dims[0] * vr.dims[1],
+                  off[0], off[1], off[2],
+                  sl->m[t][0], sl->m[t][1], sl->m[t][2]};
+  }
+  sl->hc.clear();
+  for (int i = 0; i < n; ++i) {
+    for (int q = 0; q < 5; ++q) sums_out[i][q] = 0;
+    nvox_out[i] = 0;
+    const int s[3] = {shifts[i][0], shifts[i][1], shifts[i][2]};
+    bs_hostcand h;
+    if (!cand_box(sl->m[0], sl->m[1], s, &h)) continue;
+    h.rank = i; /* caller's index, carried through the sort */
+    h.ci = 0;
+    nvox_out[i] = h.n;
+    sl->hc.push_back(h);
+  }
+  if (sl->hc.empty()) return BS_OK;
+  int rc = rtest_issue(c, sl);
+  if (rc) return rc;
+  CHK(c, hipStreamSynchronize(sl->stream));
+  flush_stats(c);
+  for (size_t i = 0; i < sl->hc.size(); ++i)
+    for (int q = 0; q < 5; ++q)
+      sums_out[sl->hc[i].rank][q] = sl->hsums[i * 5 + q];
+  sl->hc.clear();
   return BS_OK;
 }
 

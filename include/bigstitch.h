@@ -265,6 +265,20 @@ int bs_debug_peak_scan(bs_ctx *ctx, const float *pcm_host,
                        const int64_t dims[3], int mode, float v[5],
                        int64_t idx[5], int *fell_back);
 
+/* Debug-only: run the context's r-test (the integer-sum cross-correlation
+ * kernel of the candidate stage) on n <= 64 caller-chosen integer shifts
+ * {sx, sy, sz} of one pair, at downsampling 1. Candidate boxes come from
+ * the same function the candidate stage uses, without its min_overlap
+ * filter; the launch is the candidate stage's own and is timed under
+ * BS_K_CORR. sums_out[i] = {sum a, sum b, sum aa, sum bb, sum ab} over
+ * the overlap of shift i and nvox_out[i] its voxel count (all zero when
+ * the overlap is empty). Which kernel runs is fixed per context by the
+ * environment variable BS_CORR_MODE (wide | legacy) read in
+ * bs_ctx_create. */
+int bs_debug_rtest(bs_ctx *ctx, const bs_pair_desc *pair,
+                   const int32_t (*shifts)[3], int n,
+                   uint64_t (*sums_out)[5], int64_t *nvox_out);
+
 /* -------------------------------------------- interest point detection */
 
 /* Difference-of-Gaussian interest point detection on one uploaded view.

@@ -28,7 +28,7 @@ import sys
 # algorithmic read (0.474 vs 0.537 GB): float4 loads are full-counted
 # and halo rows shared between adjacent y-strips hit in L2 -> x1,
 # genuine reuse. k_rtest u16 gathers -> x1 (1.536 vs 1.48 GB alg,
-# cacheline rounding).
+# cacheline rounding). k_rtest_wide loads 16 B/lane like k_fft_pass -> x1.
 CORRECT2X = {"k_fft_x_fwd", "k_fft_x_inv", "k_fft_x_fwd_w", "k_fft_x_inv_w"}
 # map mangled display prefix -> bench kernel-stat names (fft_pass splits
 # by launch context are not distinguishable in PMC output; report under
@@ -43,6 +43,7 @@ NAME_MAP = {
     "k_fft_z_fused": ["fft_z_inv"],
     "k_peak_tile": ["peak"],
     "k_rtest": ["corr"],
+    "k_rtest_wide": ["corr"],  # BS_CORR_MODE=wide (16 B/lane -> x1)
     "k_fuse": ["fuse"],
 }
 
