@@ -8,7 +8,7 @@ LIB = bigstitcher_spark_amd/libbigstitch.so
 
 all: $(LIB) cli
 
-$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h include/bigstitch.h
+$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h bigstitcher_spark_amd/csrc/ip_match.h bigstitcher_spark_amd/csrc/bs_ransac.h include/bigstitch.h
 	$(HIPCC) $(CXXFLAGS) -shared -Iinclude $< -o $@
 
 resource-report: bigstitcher_spark_amd/csrc/bigstitch.hip
@@ -29,7 +29,7 @@ HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall
 $(HOSTDIR)/%.o: $(HOSTDIR)/%.cpp $(HOSTDIR)/%.h
 	$(CXX_HOST) $(HOSTFLAGS) -c $< -o $@
 
-cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave $(BINDIR)/detect-interestpoints
+cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave $(BINDIR)/detect-interestpoints $(BINDIR)/match-interestpoints
 
 $(BINDIR)/stitching: $(HOSTDIR)/cli_stitching.cpp $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
@@ -43,7 +43,7 @@ $(BINDIR)/affine-fusion: $(HOSTDIR)/cli_fusion.cpp $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
-$(BINDIR)/solver: $(HOSTDIR)/cli_solver.cpp $(HOSTOBJS)
+$(BINDIR)/solver: $(HOSTDIR)/cli_solver.cpp $(HOSTDIR)/bs_ipio.h $(HOSTOBJS)
 	@mkdir -p $(BINDIR)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -lz -l:libzstd.so.1
 
@@ -52,6 +52,10 @@ $(BINDIR)/resave: $(HOSTDIR)/cli_resave.cpp $(HOSTOBJS) $(LIB)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
 $(BINDIR)/detect-interestpoints: $(HOSTDIR)/cli_detect.cpp $(HOSTOBJS) $(LIB)
+	@mkdir -p $(BINDIR)
+	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+
+$(BINDIR)/match-interestpoints: $(HOSTDIR)/cli_match.cpp $(HOSTDIR)/bs_ipio.h $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
@@ -76,5 +80,7 @@ asan:
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_fusion.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/affine-fusion -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_resave.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/resave -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_detect.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/detect-interestpoints -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_match.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/match-interestpoints -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+	$(CXX_HOST) $(ASANFLAGS) -fsanitize=undefined tests/ransac_host.cpp -o $(ASANDIR)/ransac_host
 
 .PHONY: asan

@@ -21,4 +21,5 @@ from ._native import (  # noqa: F401
     FUSION_AVG_BLEND,
     FUSION_MAX_INTENSITY,
     NativeUnavailable,
+    ransac,
 )

@@ -88,11 +88,39 @@ assert _IP_DTYPE.itemsize == C.sizeof(_InterestPoint)
 LOCALIZATION = {"none": 0, "quadratic": 1}
 
 
+class _MatchParams(C.Structure):
+    _fields_ = [
+        ("num_neighbors", C.c_int32), ("redundancy", C.c_int32),
+        ("ratio_of_distance", C.c_float), ("difference_threshold", C.c_float),
+        ("limit_search_radius", C.c_int32), ("search_radius", C.c_double),
+    ]
+
+
+class _RansacParams(C.Structure):
+    _fields_ = [
+        ("model", C.c_int32), ("regularizer", C.c_int32),
+        ("lambda_", C.c_double), ("max_epsilon", C.c_double),
+        ("min_inlier_ratio", C.c_double), ("min_num_inliers", C.c_int32),
+        ("iterations", C.c_int32),
+    ]
+
+
+# numpy view of bs_match_candidate[]
+_CAND_DTYPE = np.dtype([("a", np.int32), ("b", np.int32),
+                        ("best", np.float32), ("second", np.float32)])
+assert _CAND_DTYPE.itemsize == 16
+
+FLT_MAX = float(np.finfo(np.float32).max)
+MODELS = {"none": -1, "translation": 0, "rigid": 1, "affine": 2,
+          "identity": 3}
+
+
 BS_K_NAMES = [
     "downsample", "fft_x_fwd", "fft_y_fwd", "fft_z_fwd", "fft_z_inv",
     "fft_y_inv", "fft_x_inv", "peak", "peak_merge", "corr", "subpix",
     "fuse", "synth", "pyramid", "peak_rows",
     "dog_xy", "dog_z", "dog_extrema", "dog_subpix",
+    "ip_knn", "ip_desc", "ip_match",
 ]
 _NK = len(BS_K_NAMES)
 
@@ -173,8 +201,49 @@ def load_lib():
     lib.bs_debug_dog_volume.argtypes = [C.c_void_p, C.c_int32,
                                         C.POINTER(_DogParams), C.c_void_p,
                                         C.c_int64 * 3]
+    lib.bs_match_descriptors.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+        C.POINTER(_MatchParams), C.c_void_p, C.c_size_t,
+        C.POINTER(C.c_size_t)]
+    lib.bs_debug_ip_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_int32, C.c_void_p, C.c_void_p]
+    lib.bs_debug_ip_match.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+        C.POINTER(_MatchParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bs_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
+                              C.POINTER(_RansacParams), C.c_void_p,
+                              C.c_double * 12, C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
+
+
+def ransac(pa, pb, model="affine", regularizer="rigid", lam=0.1,
+           max_epsilon=5.0, min_inlier_ratio=0.1, min_num_inliers=12,
+           iterations=10000):
+    """Host-side RANSAC (bs_ransac; no GPU, no Context) over correspondences
+    pa[i] <-> pb[i], (N,3) xyz. Returns (inlier mask bool (N,), model (3,4)
+    mapping A onto B, number of inliers); zero inliers when no consensus
+    was accepted."""
+    lib = load_lib()
+    pa = np.ascontiguousarray(pa, np.float64).reshape(-1, 3)
+    pb = np.ascontiguousarray(pb, np.float64).reshape(-1, 3)
+    if len(pa) != len(pb):
+        raise ValueError("ransac: pa and pb differ in length")
+    prm = _RansacParams(MODELS[model.lower()], MODELS[regularizer.lower()],
+                        float(lam), float(max_epsilon),
+                        float(min_inlier_ratio), int(min_num_inliers),
+                        int(iterations))
+    mask = np.zeros(len(pa), np.uint8)
+    model_out = (C.c_double * 12)()
+    n = C.c_size_t(0)
+    rc = lib.bs_ransac(pa.ctypes.data_as(C.c_void_p),
+                       pb.ctypes.data_as(C.c_void_p), len(pa), C.byref(prm),
+                       mask.ctypes.data_as(C.c_void_p), model_out,
+                       C.byref(n))
+    if rc != 0:
+        raise RuntimeError(f"bs_ransac rc={rc}")
+    return (mask.astype(bool), np.array(model_out[:]).reshape(3, 4),
+            int(n.value))
 
 
 class Context:
@@ -447,6 +516,95 @@ class Context:
             "bs_debug_dog_volume",
         )
         return out
+
+    # -- interest point matching ------------------------------------------
+    @staticmethod
+    def _match_params(num_neighbors, redundancy, ratio_of_distance,
+                      difference_threshold, search_radius):
+        return _MatchParams(int(num_neighbors), int(redundancy),
+                            float(ratio_of_distance),
+                            float(difference_threshold),
+                            0 if search_radius is None else 1,
+                            0.0 if search_radius is None
+                            else float(search_radius))
+
+    @staticmethod
+    def _pts(p):
+        return np.ascontiguousarray(p, np.float64).reshape(-1, 3)
+
+    def match_descriptors_raw(self, pts_a, pts_b, prm, capacity):
+        """ABI-level call: (structured array of min(n_found, capacity)
+        candidates, n_found)."""
+        pa, pb = self._pts(pts_a), self._pts(pts_b)
+        out = np.zeros(capacity, _CAND_DTYPE)
+        n = C.c_size_t(0)
+        self._check(
+            self._lib.bs_match_descriptors(
+                self._h, pa.ctypes.data_as(C.c_void_p), len(pa),
+                pb.ctypes.data_as(C.c_void_p), len(pb), C.byref(prm),
+                out.ctypes.data_as(C.c_void_p) if capacity else None,
+                capacity, C.byref(n)),
+            "bs_match_descriptors",
+        )
+        return out[:min(capacity, n.value)], int(n.value)
+
+    def match_descriptors(self, pts_a, pts_b, num_neighbors=3, redundancy=1,
+                          ratio_of_distance=3.0,
+                          difference_threshold=FLT_MAX, search_radius=None):
+        """Geometric descriptor matching (PRECISE_TRANSLATION) of two (N,3)
+        xyz world-coordinate point sets. Returns a dict of arrays a, b
+        (int32 indices into the inputs, sorted by (a, b)), best, second
+        (float32 descriptor distances)."""
+        prm = self._match_params(num_neighbors, redundancy, ratio_of_distance,
+                                 difference_threshold, search_radius)
+        _, n = self.match_descriptors_raw(pts_a, pts_b, prm, 0)
+        out, n2 = self.match_descriptors_raw(pts_a, pts_b, prm, n)
+        if n2 != n:
+            raise RuntimeError(
+                f"bs_match_descriptors: count changed {n} -> {n2}")
+        return {k: np.ascontiguousarray(out[k]) for k in _CAND_DTYPE.names}
+
+    def debug_ip_knn(self, pts, k):
+        """k nearest neighbours of every point within its set: (idx int32
+        (N,k), d2 float32 (N,k)). pts are used as float32 as given."""
+        p = self._pts(pts)
+        idx = np.full((len(p), k), -1, np.int32)
+        d2 = np.full((len(p), k), np.inf, np.float32)
+        self._check(
+            self._lib.bs_debug_ip_knn(
+                self._h, p.ctypes.data_as(C.c_void_p), len(p), k,
+                idx.ctypes.data_as(C.c_void_p),
+                d2.ctypes.data_as(C.c_void_p)),
+            "bs_debug_ip_knn",
+        )
+        return idx, d2
+
+    def debug_ip_match(self, pts_a, pts_b, num_neighbors=3, redundancy=1,
+                       search_radius=None):
+        """Raw descriptor scan: (best float32, second float32, best_b int32)
+        per A descriptor (point * C + subset); empty when either set has
+        fewer than n + r + 1 points."""
+        import math
+        pa, pb = self._pts(pts_a), self._pts(pts_b)
+        prm = self._match_params(num_neighbors, redundancy, 3.0, FLT_MAX,
+                                 search_radius)
+        k = num_neighbors + redundancy
+        nd = 0
+        if 1 <= num_neighbors <= k and min(len(pa), len(pb)) > k:
+            nd = len(pa) * math.comb(k, num_neighbors)
+        best = np.full(nd, np.inf, np.float32)
+        second = np.full(nd, np.inf, np.float32)
+        bi = np.full(nd, -1, np.int32)
+        self._check(
+            self._lib.bs_debug_ip_match(
+                self._h, pa.ctypes.data_as(C.c_void_p), len(pa),
+                pb.ctypes.data_as(C.c_void_p), len(pb), C.byref(prm),
+                best.ctypes.data_as(C.c_void_p),
+                second.ctypes.data_as(C.c_void_p),
+                bi.ctypes.data_as(C.c_void_p)),
+            "bs_debug_ip_match",
+        )
+        return best, second, bi
 
     # -- debug (not part of the product surface) --------------------------
     def debug_last_top5(self):

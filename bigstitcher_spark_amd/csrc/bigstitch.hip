@@ -9,7 +9,11 @@
  *     (reference SparkAffineFusion.java:602-615,627)  -> bs_fuse_blocks
  *   - DoGImgLib2.computeDoG
  *     (reference SparkInterestPointDetection.java:552-568) -> bs_detect_dog
- *     (contract = tests/dog_ref.py; section at the end of this file)
+ *     (contract = tests/dog_ref.py; section near the end of this file)
+ *   - RGLDMPairwise descriptor matching (reference
+ *     SparkGeometricDescriptorMatching.java:594-604) -> bs_match_descriptors
+ *     (contract = tests/match_ref.py; csrc/ip_match.h, included last) and
+ *     the RANSAC behind it -> bs_ransac (host only; csrc/bs_ransac.h)
  *
  * Arithmetic contract = oracle/phasecorr.py and oracle/fusion.py (the CPU
  * restatement; see its [PIN-*] notes). Shifts must match the oracle within
@@ -2492,6 +2496,10 @@ struct bs_ctx {
   unsigned int *dog_cnt = nullptr;
   size_t dog_cnt_cap = 0;
   size_t dog_init_cap = 65536; /* first candidate capacity (BS_DOG_INIT_CAP) */
+  /* interest-point matching scratch (ip_match.h, indexed by IPB_*) */
+  void *ip_buf[12] = {};
+  size_t ip_cap[12] = {};
+  int ip_split = 0; /* BS_IP_SPLIT: forced number of B slices, 0 = auto */
   /* stats */
   bs_batch_stats stats{};
   std::vector<bs_ev> evs;
@@ -2557,6 +2565,10 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   if (const char *e = getenv("BS_DOG_INIT_CAP")) {
     long v = atol(e);
     if (v >= 1) c->dog_init_cap = (size_t)v;
+  }
+  if (const char *e = getenv("BS_IP_SPLIT")) {
+    int v = atoi(e);
+    if (v >= 1) c->ip_split = v;
   }
   if (hipSetDevice(device_id) != hipSuccess ||
       hipStreamCreate(&c->stream) != hipSuccess ||
@@ -2687,6 +2699,7 @@ extern "C" void bs_ctx_destroy(bs_ctx *c) {
   (void)hipFree(c->dog_cand);
   (void)hipFree(c->dog_pts);
   (void)hipFree(c->dog_cnt);
+  for (void *b : c->ip_buf) (void)hipFree(b);
   (void)hipStreamDestroy(c->stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   delete c;
@@ -4968,3 +4981,11 @@ extern "C" int bs_detect_dog(bs_ctx *c, int32_t view_id,
   }
   return BS_OK;
 }
+
+/*********************************************************************
+ *  Interest point matching (bs_match_descriptors) and RANSAC         *
+ *********************************************************************/
+#include "ip_match.h"
+static_assert(IPB_COUNT <= sizeof(bs_ctx::ip_buf) / sizeof(void *),
+              "bs_ctx::ip_buf too small");
+#include "bs_ransac.h"

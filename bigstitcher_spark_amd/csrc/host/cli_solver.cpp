@@ -15,21 +15,62 @@
  * d_link: the stored link matrix's translation ws satisfies
  * "B's content appears at +ws relative to where the current
  * registrations place it" is ws = -correction, i.e. the solved
- * adjustment should satisfy t_B - t_A = -ws. */
+ * adjustment should satisfy t_B - t_A = -ws.
+ *
+ * -s/--sourcePoints IP (Solver.java:434-670) takes the links from the
+ * corresponding interest points `match-interestpoints` stored instead
+ * ([PIN-IPCORR], bs_ipio.h): for each view pair A < B and each -l label,
+ * A's correspondence list gives d = mean(pA_world - pB_world) over its
+ * matches with B, weighted by match count x label weight (-lw); the
+ * prepended transform is then named "Interest Point Transform"
+ * ([PIN-XML] restatement). Only -tm TRANSLATION is built. Without -s (or
+ * with -s STITCHING) nothing changes. */
 #include <cmath>
+#include <array>
 #include <cstdio>
+#include <map>
 #include <set>
 
 #include "bs_cli_util.h"
+#include "bs_ipio.h"
 #include "bs_spimdata.h"
 
 int main(int argc, char **argv) {
   bscli::Args args;
-  std::map<std::string, std::string> alias = {{"-x", "--xml"}};
+  std::map<std::string, std::string> alias = {
+      {"-x", "--xml"},           {"-s", "--sourcePoints"},
+      {"-l", "--label"},         {"-lw", "--labelweights"},
+      {"-tm", "--transformationModel"}};
   if (!args.parse(argc, argv, alias, {"dryRun"}) || !args.has("xml")) {
     fprintf(stderr,
-            "usage: solver -x dataset.xml [--fixedViews tp,setup[;..]] "
-            "[--minR 0.3] [--dryRun]\n");
+            "usage: solver -x dataset.xml [-s STITCHING|IP] [-l label ..] "
+            "[-lw weight ..] [--fixedViews tp,setup[;..]] [--minR 0.3] "
+            "[--dryRun]\n");
+    return 2;
+  }
+  const std::string source = args.get("sourcePoints", "STITCHING");
+  if (source != "STITCHING" && source != "IP") {
+    fprintf(stderr, "error: unknown --sourcePoints %s (STITCHING|IP)\n",
+            source.c_str());
+    return 2;
+  }
+  const bool use_ip = source == "IP";
+  if (args.get("transformationModel", "TRANSLATION") != "TRANSLATION") {
+    fprintf(stderr,
+            "error: -tm %s is not supported by this build (TRANSLATION "
+            "only)\n",
+            args.get("transformationModel").c_str());
+    return 2;
+  }
+  const std::vector<std::string> labels = args.getall("label");
+  std::vector<double> label_w;
+  for (auto &w : args.getall("labelweights")) label_w.push_back(atof(w.c_str()));
+  if (use_ip && labels.empty()) {
+    fprintf(stderr, "error: -s IP needs at least one -l label\n");
+    return 2;
+  }
+  if (use_ip && !label_w.empty() && label_w.size() != labels.size()) {
+    fprintf(stderr, "error: give one -lw weight per -l label\n");
     return 2;
   }
   bssd::SpimData sd;
@@ -39,8 +80,11 @@ int main(int argc, char **argv) {
     return 1;
   }
   double minR = args.getd("minR", 0.3);
-  auto entries = sd.stitching_results();
-  printf("solver: %zu stitching links loaded\n", entries.size());
+  std::vector<bssd::StitchEntry> entries;
+  if (!use_ip) {
+    entries = sd.stitching_results();
+    printf("solver: %zu stitching links loaded\n", entries.size());
+  }
 
   /* view index map over (tp, setup) present in registrations */
   std::vector<bssd::ViewId> ids;
@@ -88,8 +132,78 @@ int main(int argc, char **argv) {
     l.w = std::max(0.0, e.r);
     links.push_back(l);
   }
-  printf("solver: %zu usable links (%zu stale-hash, %zu below minR)\n",
-         links.size(), dropped_hash, dropped_r);
+  if (use_ip) {
+    const std::string ipn5 = bsip::ipn5_path(args.get("xml"));
+    bsn5::Container c(ipn5);
+    std::set<std::pair<bssd::ViewId, std::string>> have;
+    for (auto &e : sd.interest_points())
+      have.insert({{e.timepoint, e.setup}, e.label});
+    size_t matches = 0;
+    for (size_t li = 0; li < labels.size(); ++li) {
+      const std::string &label = labels[li];
+      const double lw = label_w.empty() ? 1.0 : label_w[li];
+      /* id -> world location per view */
+      std::map<bssd::ViewId, std::map<uint64_t, std::array<double, 3>>> world;
+      for (auto &v : ids) {
+        if (!have.count({v, label})) continue;
+        std::vector<uint64_t> pid;
+        std::vector<double> loc;
+        const std::string group =
+            bssd::SpimData::interest_point_group(v.first, v.second, label);
+        if (!bsip::read_points(c, group, &pid, &loc)) {
+          fprintf(stderr, "error: cannot read %s/%s\n", ipn5.c_str(),
+                  group.c_str());
+          return 1;
+        }
+        const auto &m = sd.regs.at(v);
+        auto &w = world[v];
+        for (size_t i = 0; i < pid.size(); ++i) {
+          std::array<double, 3> p;
+          for (int r = 0; r < 3; ++r)
+            p[r] = m[4 * r] * loc[3 * i] + m[4 * r + 1] * loc[3 * i + 1] +
+                   m[4 * r + 2] * loc[3 * i + 2] + m[4 * r + 3];
+          w[pid[i]] = p;
+        }
+      }
+      for (auto &va : world) { /* A's list only, partners B > A */
+        std::vector<bsip::Corr> list;
+        const std::string group = bssd::SpimData::interest_point_group(
+            va.first.first, va.first.second, label);
+        if (!bsip::read_corrs(c, group, &list)) {
+          fprintf(stderr, "error: inconsistent correspondences in %s/%s\n",
+                  ipn5.c_str(), group.c_str());
+          return 1;
+        }
+        std::map<bssd::ViewId, std::pair<std::array<double, 3>, size_t>> acc;
+        for (auto &k : list) {
+          if (k.other_label != label || !(va.first < k.other)) continue;
+          auto wb = world.find(k.other);
+          if (wb == world.end()) continue;
+          auto pa = va.second.find(k.id);
+          auto pb = wb->second.find(k.other_id);
+          if (pa == va.second.end() || pb == wb->second.end()) continue;
+          auto &a = acc[k.other];
+          for (int d = 0; d < 3; ++d) a.first[d] += pa->second[d] - pb->second[d];
+          ++a.second;
+        }
+        for (auto &kv : acc) {
+          Link l;
+          l.a = idx[va.first];
+          l.b = idx[kv.first];
+          for (int d = 0; d < 3; ++d)
+            l.d[d] = kv.second.first[d] / (double)kv.second.second;
+          l.w = (double)kv.second.second * lw;
+          links.push_back(l);
+          matches += kv.second.second;
+        }
+      }
+    }
+    printf("solver: %zu interest point links from %zu matches\n",
+           links.size(), matches);
+  } else {
+    printf("solver: %zu usable links (%zu stale-hash, %zu below minR)\n",
+           links.size(), dropped_hash, dropped_r);
+  }
   if (links.empty()) {
     fprintf(stderr, "nothing to solve\n");
     return 1;
@@ -183,7 +297,8 @@ int main(int argc, char **argv) {
     auto vt = std::make_shared<bsx::Node>();
     vt->tag = "ViewTransform";
     vt->attrs["type"] = "affine";
-    vt->add_text("Name", "Stitching Transform");
+    vt->add_text("Name",
+                 use_ip ? "Interest Point Transform" : "Stitching Transform");
     vt->add_text("affine", aff);
     vr->children.insert(vr->children.begin(), vt);
   }

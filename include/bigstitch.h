@@ -347,6 +347,86 @@ int bs_debug_dog_volume(bs_ctx *ctx, int32_t view_id,
                         const bs_dog_params *params, float *out,
                         int64_t out_dims[3]);
 
+/* --------------------------------------------- interest point matching */
+
+/* Geometric descriptor matching of two interest-point sets (the reference's
+ * PRECISE_TRANSLATION method). Replaces the in-process call site
+ *   net.preibisch.mvrecon...RGLDMPairwise.match(listA, listB)
+ * constructed at reference SparkGeometricDescriptorMatching.java:594-604.
+ * RGLDMPairwise is not part of the reference tree, so the arithmetic is this
+ * project's restatement, pinned by tests/match_ref.py (tags [PIN-F32PTS],
+ * [PIN-KNN], [PIN-RGLDM], [PIN-DESCDIST], [PIN-RATIO], [PIN-AMBIG] are
+ * spelled out there). Device arithmetic is float32. */
+typedef struct {
+  int32_t num_neighbors;       /* n, default 3 */
+  int32_t redundancy;          /* r, default 1 */
+  float   ratio_of_distance;   /* --significance, default 3 */
+  float   difference_threshold;/* default FLT_MAX */
+  int32_t limit_search_radius; double search_radius;
+} bs_match_params;
+typedef struct { int32_t a, b; float best, second; } bs_match_candidate;
+
+/* pts_a / pts_b: na / nb points, {x,y,z} double world coordinates. Writes
+ * min(*n_found, capacity) candidates sorted by (a, b) and always sets
+ * *n_found to the full count (out may be NULL when capacity == 0; call twice
+ * to size the buffer). a / b index the input arrays; best / second are those
+ * of the pair's descriptor match with the smallest best. A set with fewer
+ * than n + r + 1 points gives zero candidates. The same arguments give
+ * bit-identical arrays on every call.
+ * Errors: BS_EUNSUP unless n >= 1, r >= 0, n + r <= 8, n <= 6, and when a
+ * set has 2^31 descriptors or more; BS_EINVAL for a non-finite coordinate or
+ * a negative search radius. */
+int bs_match_descriptors(bs_ctx *ctx, const double *pts_a, size_t na,
+                         const double *pts_b, size_t nb,
+                         const bs_match_params *params,
+                         bs_match_candidate *out, size_t capacity,
+                         size_t *n_found);
+
+/* Debug-only (parity tooling): k nearest neighbours of every point within
+ * its set ([PIN-KNN]), 1 <= k <= 8. pts are rounded to float32 as given (no
+ * minimum is subtracted: pass [PIN-F32PTS] values). idx_out int32 [n][k],
+ * d2_out float [n][k]; with n <= k every entry is -1 / +inf. */
+int bs_debug_ip_knn(bs_ctx *ctx, const double *pts, size_t n, int32_t k,
+                    int32_t *idx_out, float *d2_out);
+
+/* Debug-only: the raw result of the descriptor scan, one entry per A
+ * descriptor (na * C of them, C = C(n + r, n); index = point * C + subset):
+ * best, second (+inf where missing) and best_b (B descriptor index, -1 if
+ * none). Nothing is written when either set has fewer than n + r + 1
+ * points. The scan's split of B over the grid is chosen from the sizes;
+ * the environment variable BS_IP_SPLIT (read in bs_ctx_create) forces a
+ * number of slices, 1 = one scan per A descriptor. */
+int bs_debug_ip_match(bs_ctx *ctx, const double *pts_a, size_t na,
+                      const double *pts_b, size_t nb,
+                      const bs_match_params *params, float *best_out,
+                      float *second_out, int32_t *best_b_out);
+
+/* Host-only RANSAC over correspondences ([PIN-RANSAC]; needs no context and
+ * no GPU; csrc/bs_ransac.h). pa[i] <-> pb[i], {x,y,z} doubles; the model
+ * maps A onto B: pb ~ M * (pa, 1), M row-major 3x4. */
+#define BS_MODEL_NONE -1       /* regularizer only */
+#define BS_MODEL_TRANSLATION 0
+#define BS_MODEL_RIGID 1
+#define BS_MODEL_AFFINE 2
+#define BS_MODEL_IDENTITY 3    /* regularizer only */
+typedef struct {
+  int32_t model;            /* -tm, default AFFINE */
+  int32_t regularizer;      /* -rm, default RIGID */
+  double lambda;            /* default 0.1 */
+  double max_epsilon;       /* -rme, default 5.0 */
+  double min_inlier_ratio;  /* -rmir, default 0.1 */
+  int32_t min_num_inliers;  /* -rmni, default 12 */
+  int32_t iterations;       /* -rit, default 10000 */
+} bs_ransac_params;
+
+/* inlier_out (n bytes, optional) receives 1 for inliers; model_out
+ * (optional) the model refitted on them; *n_inliers their count. Returns
+ * BS_OK with *n_inliers = 0 (mask zero, model identity) when no consensus is
+ * accepted. Deterministic: fixed seed, same input -> same output. */
+int bs_ransac(const double *pa, const double *pb, size_t n,
+              const bs_ransac_params *params, uint8_t *inlier_out,
+              double model_out[12], size_t *n_inliers);
+
 /* ------------------------------------------------------- instrumentation */
 
 /* Per-kernel timing, HIP-event measured on the launch stream (bench.py
@@ -374,6 +454,9 @@ enum bs_kernel_id {
   BS_K_DOG_Z,       /* z pass for both sigmas + subtract + scale -> D */
   BS_K_DOG_EXTREMA, /* 3x3x3 strict extremum scan + gate + compaction */
   BS_K_DOG_SUBPIX,  /* per-candidate quadratic fit + intensity sample */
+  BS_K_IP_KNN,      /* brute-force k nearest neighbours within a point set */
+  BS_K_IP_DESC,     /* descriptor gather */
+  BS_K_IP_MATCH,    /* best / second descriptor scan (+ slice merge) */
   BS_K_COUNT
 };
 
