@@ -8,7 +8,7 @@ LIB = bigstitcher_spark_amd/libbigstitch.so
 
 all: $(LIB) cli
 
-$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h bigstitcher_spark_amd/csrc/ip_match.h bigstitcher_spark_amd/csrc/bs_ransac.h include/bigstitch.h
+$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h bigstitcher_spark_amd/csrc/ip_match.h bigstitcher_spark_amd/csrc/bs_ransac.h bigstitcher_spark_amd/csrc/intensity_match.h bigstitcher_spark_amd/csrc/bs_intensity_solve.h include/bigstitch.h
 	$(HIPCC) $(CXXFLAGS) -shared -Iinclude $< -o $@
 
 resource-report: bigstitcher_spark_amd/csrc/bigstitch.hip
@@ -29,7 +29,7 @@ HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall
 $(HOSTDIR)/%.o: $(HOSTDIR)/%.cpp $(HOSTDIR)/%.h
 	$(CXX_HOST) $(HOSTFLAGS) -c $< -o $@
 
-cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave $(BINDIR)/detect-interestpoints $(BINDIR)/match-interestpoints
+cli: $(BINDIR)/stitching $(BINDIR)/create-fusion-container $(BINDIR)/affine-fusion $(BINDIR)/solver $(BINDIR)/resave $(BINDIR)/detect-interestpoints $(BINDIR)/match-interestpoints $(BINDIR)/match-intensities $(BINDIR)/solve-intensities
 
 $(BINDIR)/stitching: $(HOSTDIR)/cli_stitching.cpp $(HOSTOBJS) $(LIB)
 	@mkdir -p $(BINDIR)
@@ -59,6 +59,14 @@ $(BINDIR)/match-interestpoints: $(HOSTDIR)/cli_match.cpp $(HOSTDIR)/bs_ipio.h $(
 	@mkdir -p $(BINDIR)
 	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
+$(BINDIR)/match-intensities: $(HOSTDIR)/cli_intensity_match.cpp $(HOSTDIR)/bs_intio.h $(HOSTOBJS) $(LIB)
+	@mkdir -p $(BINDIR)
+	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+
+$(BINDIR)/solve-intensities: $(HOSTDIR)/cli_intensity_solve.cpp $(HOSTDIR)/bs_intio.h bigstitcher_spark_amd/csrc/bs_intensity_solve.h $(HOSTOBJS)
+	@mkdir -p $(BINDIR)
+	$(CXX_HOST) $(HOSTFLAGS) -Iinclude $< $(HOSTOBJS) -o $@ -lz -l:libzstd.so.1
+
 clean-cli:
 	rm -f $(HOSTOBJS) $(BINDIR)/*
 
@@ -82,5 +90,7 @@ asan:
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_detect.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/detect-interestpoints -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_match.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/match-interestpoints -Lbigstitcher_spark_amd -lbigstitch -lz -l:libzstd.so.1 -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 	$(CXX_HOST) $(ASANFLAGS) -fsanitize=undefined tests/ransac_host.cpp -o $(ASANDIR)/ransac_host
+	$(CXX_HOST) $(ASANFLAGS) -Iinclude $(HOSTDIR)/cli_intensity_solve.cpp $(HOSTDIR)/bs_json.cpp $(HOSTDIR)/bs_n5.cpp $(HOSTDIR)/bs_zarr.cpp $(HOSTDIR)/bs_xml.cpp $(HOSTDIR)/bs_spimdata.cpp -o $(ASANDIR)/solve-intensities -lz -l:libzstd.so.1
+	$(CXX_HOST) $(ASANFLAGS) -fsanitize=undefined tests/intensity_solve_host.cpp -o $(ASANDIR)/intensity_solve_host
 
 .PHONY: asan

@@ -21,5 +21,6 @@ from ._native import (  # noqa: F401
     FUSION_AVG_BLEND,
     FUSION_MAX_INTENSITY,
     NativeUnavailable,
+    intensity_solve,
     ransac,
 )

@@ -105,6 +105,32 @@ class _RansacParams(C.Structure):
     ]
 
 
+class _IntensityParams(C.Structure):
+    _fields_ = [
+        ("render_scale", C.c_double), ("coefficients", C.c_int32 * 3),
+        ("min_num_candidates", C.c_int32), ("min_threshold", C.c_double),
+        ("max_threshold", C.c_double), ("iterations", C.c_int32),
+        ("min_num_inliers", C.c_int32), ("max_epsilon", C.c_double),
+        ("min_inlier_ratio", C.c_double),
+    ]
+
+
+class _IntensitySolveParams(C.Structure):
+    _fields_ = [
+        ("lambda_identity", C.c_double), ("lambda_smooth", C.c_double),
+        ("max_iterations", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+
+# numpy view of bs_intensity_match[]
+INTENSITY_MATCH_DTYPE = np.dtype(
+    [(k, np.uint64) for k in ("cell_a", "cell_b", "n_cand", "n_inl",
+                              "best_it", "n_inl_first", "sp", "sq", "spp",
+                              "sqq", "spq")]
+    + [("a", np.float64), ("b", np.float64)])
+assert INTENSITY_MATCH_DTYPE.itemsize == 104
+
+
 # numpy view of bs_match_candidate[]
 _CAND_DTYPE = np.dtype([("a", np.int32), ("b", np.int32),
                         ("best", np.float32), ("second", np.float32)])
@@ -120,6 +146,7 @@ BS_K_NAMES = [
     "fft_y_inv", "fft_x_inv", "peak", "peak_merge", "corr", "subpix",
     "fuse", "synth", "pyramid", "peak_rows",
     "dog_xy", "dog_z", "dog_extrema", "dog_subpix",
+    "int_render", "int_moments", "int_ransac",
     "ip_knn", "ip_desc", "ip_match",
 ]
 _NK = len(BS_K_NAMES)
@@ -213,8 +240,57 @@ def load_lib():
     lib.bs_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
                               C.POINTER(_RansacParams), C.c_void_p,
                               C.c_double * 12, C.POINTER(C.c_size_t)]
+    lib.bs_intensity_match_pair.argtypes = [
+        C.c_void_p, C.c_int32, C.c_double * 12, C.c_int32, C.c_double * 12,
+        C.POINTER(_IntensityParams), C.c_void_p, C.c_size_t,
+        C.POINTER(C.c_size_t)]
+    lib.bs_debug_intensity_render.argtypes = [
+        C.c_void_p, C.c_int32, C.c_double * 12, C.c_int32, C.c_double * 12,
+        C.POINTER(_IntensityParams), C.c_int64 * 3, C.c_int64 * 3,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bs_intensity_solve.argtypes = [
+        C.c_int32, C.c_int32 * 3, C.c_void_p, C.c_void_p, C.c_size_t,
+        C.c_void_p, C.POINTER(_IntensitySolveParams), C.c_void_p,
+        C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     _lib = lib
     return lib
+
+
+def intensity_solve(nviews, coefficients, pairs, lambda_identity=0.01,
+                    lambda_smooth=0.1, max_iterations=1000):
+    """Host-side global intensity solve (bs_intensity_solve; no GPU, no
+    Context). pairs: list of (view_a, view_b, matches) with view indices in
+    0..nviews-1 and matches an INTENSITY_MATCH_DTYPE array as returned by
+    Context.intensity_match_pair(view_a, .., view_b, ..). Returns
+    (coeff float64 (nviews, 2, gz, gy, gx), iterations, relative residual);
+    coeff[v, 0] multiplies, coeff[v, 1] adds (grey levels)."""
+    lib = load_lib()
+    cg = [int(v) for v in coefficients]
+    ncell = cg[0] * cg[1] * cg[2]
+    pv = np.zeros((len(pairs), 2), np.int32)
+    offs = np.zeros(len(pairs) + 1, np.uintp)
+    chunks = []
+    for k, (va, vb, m) in enumerate(pairs):
+        pv[k] = (va, vb)
+        m = np.ascontiguousarray(m, INTENSITY_MATCH_DTYPE)
+        chunks.append(m)
+        offs[k + 1] = offs[k] + len(m)
+    allm = (np.concatenate(chunks) if chunks
+            else np.zeros(0, INTENSITY_MATCH_DTYPE))
+    prm = _IntensitySolveParams(float(lambda_identity), float(lambda_smooth),
+                                int(max_iterations), 0)
+    out = np.zeros((int(nviews), 2 * ncell), np.float64)
+    it = C.c_int32(0)
+    rr = C.c_double(0.0)
+    rc = lib.bs_intensity_solve(
+        int(nviews), (C.c_int32 * 3)(*cg), pv.ctypes.data_as(C.c_void_p),
+        offs.ctypes.data_as(C.c_void_p), len(pairs),
+        allm.ctypes.data_as(C.c_void_p), C.byref(prm),
+        out.ctypes.data_as(C.c_void_p), C.byref(it), C.byref(rr))
+    if rc != 0:
+        raise RuntimeError(f"bs_intensity_solve rc={rc}")
+    return (out.reshape(int(nviews), 2, cg[2], cg[1], cg[0]), int(it.value),
+            float(rr.value))
 
 
 def ransac(pa, pb, model="affine", regularizer="rigid", lam=0.1,
@@ -607,6 +683,89 @@ class Context:
         return best, second, bi
 
     # -- debug (not part of the product surface) --------------------------
+    @staticmethod
+    def _intensity_params(render_scale, coefficients, min_num_candidates,
+                          min_threshold, max_threshold, iterations,
+                          max_epsilon, min_inlier_ratio, min_num_inliers):
+        return _IntensityParams(
+            float(render_scale), (C.c_int32 * 3)(*[int(v) for v in
+                                                   coefficients]),
+            int(min_num_candidates), float(min_threshold),
+            float("nan") if max_threshold is None else float(max_threshold),
+            int(iterations), int(min_num_inliers), float(max_epsilon),
+            float(min_inlier_ratio))
+
+    @staticmethod
+    def _affine12(m):
+        m = np.ascontiguousarray(m, np.float64).reshape(-1)
+        if m.size != 12:
+            raise ValueError("affine must be 3x4")
+        return (C.c_double * 12)(*m)
+
+    def intensity_match_pair_raw(self, view_a, affine_a, view_b, affine_b,
+                                 prm, capacity):
+        """One bs_intensity_match_pair call with a buffer of `capacity`
+        records: (rc, records written, n_found)."""
+        buf = np.zeros(max(int(capacity), 1), INTENSITY_MATCH_DTYPE)
+        n = C.c_size_t(0)
+        rc = self._lib.bs_intensity_match_pair(
+            self._h, view_a, self._affine12(affine_a), view_b,
+            self._affine12(affine_b), C.byref(prm),
+            buf.ctypes.data_as(C.c_void_p) if capacity else None,
+            int(capacity), C.byref(n))
+        return rc, buf[:min(int(capacity), n.value)], int(n.value)
+
+    def intensity_match_pair(self, view_a, affine_a, view_b, affine_b,
+                             render_scale=0.25, coefficients=(8, 8, 8),
+                             min_num_candidates=1000, min_threshold=1.0,
+                             max_threshold=None, iterations=1000,
+                             max_epsilon=5.1, min_inlier_ratio=0.1,
+                             min_num_inliers=10):
+        """Intensity matches of two uploaded views (bs_intensity_match_pair):
+        an INTENSITY_MATCH_DTYPE array sorted by (cell_a, cell_b)."""
+        prm = self._intensity_params(render_scale, coefficients,
+                                     min_num_candidates, min_threshold,
+                                     max_threshold, iterations, max_epsilon,
+                                     min_inlier_ratio, min_num_inliers)
+        # one call is enough unless more buckets come back than guessed
+        rc, got, n = self.intensity_match_pair_raw(view_a, affine_a, view_b,
+                                                   affine_b, prm, 1024)
+        self._check(rc, "bs_intensity_match_pair")
+        if n > len(got):
+            rc, got, n2 = self.intensity_match_pair_raw(
+                view_a, affine_a, view_b, affine_b, prm, n)
+            self._check(rc, "bs_intensity_match_pair")
+            assert n2 == n
+        return got.copy()
+
+    def debug_intensity_render(self, view_a, affine_a, view_b, affine_b,
+                               render_scale=0.25, coefficients=(8, 8, 8),
+                               min_threshold=1.0, max_threshold=None):
+        """The render stage alone: dict(origin, dims (x,y,z), P, Q int32 and
+        cell_a, cell_b uint16 arrays of shape (gz, gy, gx))."""
+        prm = self._intensity_params(render_scale, coefficients, 1,
+                                     min_threshold, max_threshold, 1, 1.0,
+                                     0.0, 1)
+        g0 = (C.c_int64 * 3)()
+        gd = (C.c_int64 * 3)()
+        fa, fb = self._affine12(affine_a), self._affine12(affine_b)
+        self._check(self._lib.bs_debug_intensity_render(
+            self._h, view_a, fa, view_b, fb, C.byref(prm), g0, gd, None,
+            None, None, None), "bs_debug_intensity_render")
+        shape = (gd[2], gd[1], gd[0])
+        P = np.zeros(shape, np.int32)
+        Q = np.zeros(shape, np.int32)
+        ca = np.zeros(shape, np.uint16)
+        cb = np.zeros(shape, np.uint16)
+        if P.size:
+            self._check(self._lib.bs_debug_intensity_render(
+                self._h, view_a, fa, view_b, fb, C.byref(prm), g0, gd,
+                P.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p),
+                ca.ctypes.data_as(C.c_void_p),
+                cb.ctypes.data_as(C.c_void_p)), "bs_debug_intensity_render")
+        return dict(origin=tuple(g0), dims=tuple(gd), P=P, Q=Q, cell_a=ca,
+                    cell_b=cb)
+
     def debug_last_top5(self):
         """Top five PCM maxima of the last stitched pair as the candidate
         stage received them: (values float32[5], linear indices int64[5])."""

@@ -2500,6 +2500,9 @@ struct bs_ctx {
   void *ip_buf[12] = {};
   size_t ip_cap[12] = {};
   int ip_split = 0; /* BS_IP_SPLIT: forced number of B slices, 0 = auto */
+  /* intensity matching scratch (intensity_match.h, indexed by INTB_*) */
+  void *int_buf[8] = {};
+  size_t int_cap[8] = {};
   /* stats */
   bs_batch_stats stats{};
   std::vector<bs_ev> evs;
@@ -2700,6 +2703,7 @@ extern "C" void bs_ctx_destroy(bs_ctx *c) {
   (void)hipFree(c->dog_pts);
   (void)hipFree(c->dog_cnt);
   for (void *b : c->ip_buf) (void)hipFree(b);
+  for (void *b : c->int_buf) (void)hipFree(b);
   (void)hipStreamDestroy(c->stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   delete c;
@@ -4989,3 +4993,10 @@ extern "C" int bs_detect_dog(bs_ctx *c, int32_t view_id,
 static_assert(IPB_COUNT <= sizeof(bs_ctx::ip_buf) / sizeof(void *),
               "bs_ctx::ip_buf too small");
 #include "bs_ransac.h"
+
+/*********************************************************************
+ *  Intensity matching (bs_intensity_match_pair) and the host solve   *
+ *********************************************************************/
+#include "intensity_match.h"
+static_assert(INTB_COUNT <= sizeof(bs_ctx::int_buf) / sizeof(void *),
+              "bs_ctx::int_buf too small");

@@ -427,6 +427,100 @@ int bs_ransac(const double *pa, const double *pb, size_t n,
               const bs_ransac_params *params, uint8_t *inlier_out,
               double model_out[12], size_t *n_inliers);
 
+/* ----------------------------------------------------- intensity matching */
+
+/* Pairwise intensity matching of two overlapping views. Replaces the
+ * in-process call site
+ *   net.preibisch.mvrecon...IntensityCorrection.matchRansac(data, v1, v2,
+ *       renderScale, coefficientsSize, minThreshold, maxThreshold,
+ *       minNumCandidates, iterations, maxEpsilon, minInlierRatio,
+ *       minNumInliers, maxTrust)
+ * of reference SparkIntensityMatching.java:173-174. IntensityCorrection is
+ * not part of the reference tree, so the arithmetic is this project's
+ * restatement, pinned by tests/intensity_ref.py; the tags [PIN-INT-GRID],
+ * [PIN-INT-RENDER], [PIN-INT-CELL], [PIN-INT-RANSAC], [PIN-INT-TRUST] and
+ * [PIN-INT-SOLVE] are spelled out in DESIGN.md "Intensity matching". Both
+ * views are sampled on a coarse world grid; samples are quantised to integers P (view A) and
+ * Q (view B) in 1/8 grey level and bucketed by the pair of coefficient
+ * cells they fall in; each bucket gets a line Q = a P + b by RANSAC and
+ * integer-moment refits. Every result is an integer or a fixed formula of
+ * integers, so the same arguments give the same bits on every call. */
+typedef struct {
+  double render_scale;        /* --renderScale, in (0, 1], default 0.25 */
+  int32_t coefficients[3];    /* --numCoefficients, cells per axis {x,y,z} */
+  int32_t min_num_candidates; /* default 1000 */
+  double min_threshold;       /* grey levels, default 1 */
+  double max_threshold;       /* grey levels, NaN = none (default) */
+  int32_t iterations;         /* 1 .. 4096, default 1000 */
+  int32_t min_num_inliers;    /* default 10 */
+  double max_epsilon;         /* grey levels, default 5.1 */
+  double min_inlier_ratio;    /* default 0.1 */
+} bs_intensity_params;
+
+/* One accepted bucket. Moments are over the final inlier set, in units of
+ * 1/8 grey level (sp = sum P, spq = sum P*Q, ...). a, b: Q/8 = a * P/8 + b,
+ * b in grey levels; both follow from n_inl and the moments alone. */
+typedef struct {
+  uint64_t cell_a, cell_b;  /* linear cell ids, x fastest */
+  uint64_t n_cand, n_inl;
+  uint64_t best_it;         /* winning RANSAC iteration */
+  uint64_t n_inl_first;     /* its inlier count, before any refit */
+  uint64_t sp, sq, spp, sqq, spq;
+  double a, b;
+} bs_intensity_match;
+
+/* Writes min(*n_found, capacity) buckets sorted by (cell_a, cell_b) and
+ * always sets *n_found to the full count (out may be NULL when capacity ==
+ * 0; call twice to size the buffer). affine_a / affine_b: row-major 3x4,
+ * view-local -> world. Views whose transformed boxes do not intersect give
+ * zero buckets and BS_OK.
+ * Errors: BS_ENOVIEW unknown view; BS_EINVAL render_scale not in (0, 1], a
+ * cell count < 1, iterations < 1, a singular affine; BS_EUNSUP more than
+ * 65535 cells per view, more than 2^31 grid samples, a bucket above 2^24
+ * members (the u64 moment bound), iterations > 4096. */
+int bs_intensity_match_pair(bs_ctx *ctx, int32_t view_a,
+                            const double affine_a[12], int32_t view_b,
+                            const double affine_b[12],
+                            const bs_intensity_params *params,
+                            bs_intensity_match *out, size_t capacity,
+                            size_t *n_found);
+
+/* Debug-only (parity tooling): the render stage alone. grid_origin / grid_dims
+ * receive g0 and dims of [PIN-INT-GRID] (dims all zero when the boxes are
+ * disjoint); with p_out == NULL only they are returned. Otherwise p_out,
+ * q_out (int32) and cell_a_out, cell_b_out (uint16) receive prod(dims)
+ * samples, x fastest; invalid samples carry P = Q = -1. */
+int bs_debug_intensity_render(bs_ctx *ctx, int32_t view_a,
+                              const double affine_a[12], int32_t view_b,
+                              const double affine_b[12],
+                              const bs_intensity_params *params,
+                              int64_t grid_origin[3], int64_t grid_dims[3],
+                              int32_t *p_out, int32_t *q_out,
+                              uint16_t *cell_a_out, uint16_t *cell_b_out);
+
+/* Host-only global solve ([PIN-INT-SOLVE]; needs no context and no GPU;
+ * csrc/bs_intensity_solve.h). Pair k joins views pair_views[2k] (its A
+ * side) and pair_views[2k+1], indices in 0 .. nviews-1, and owns
+ * matches[pair_offsets[k] .. pair_offsets[k+1]); only the integer fields of
+ * a match are read. coeff_out: nviews * 2 * ncells doubles, per view the
+ * multiplicative plane then the additive plane (grey levels), cells x
+ * fastest — the layout bs_view_set_coefficients takes. iterations_out and
+ * rel_residual_out are optional. Errors: BS_EINVAL for a cell count < 1, a
+ * view index or cell id out of range, max_iterations < 1. */
+typedef struct {
+  double lambda_identity; /* default 0.01 */
+  double lambda_smooth;   /* default 0.1 */
+  int32_t max_iterations; /* default 1000 */
+  int32_t _pad;
+} bs_intensity_solve_params;
+
+int bs_intensity_solve(int32_t nviews, const int32_t coefficients[3],
+                       const int32_t *pair_views, const size_t *pair_offsets,
+                       size_t npairs, const bs_intensity_match *matches,
+                       const bs_intensity_solve_params *params,
+                       double *coeff_out, int32_t *iterations_out,
+                       double *rel_residual_out);
+
 /* ------------------------------------------------------- instrumentation */
 
 /* Per-kernel timing, HIP-event measured on the launch stream (bench.py
@@ -454,6 +548,11 @@ enum bs_kernel_id {
   BS_K_DOG_Z,       /* z pass for both sigmas + subtract + scale -> D */
   BS_K_DOG_EXTREMA, /* 3x3x3 strict extremum scan + gate + compaction */
   BS_K_DOG_SUBPIX,  /* per-candidate quadratic fit + intensity sample */
+  /* intensity matching; placed ahead of the interest-point matching ids,
+   * which stay the last three before BS_K_COUNT */
+  BS_K_INT_RENDER,  /* both views sampled on the coarse world grid */
+  BS_K_INT_MOMENTS, /* per-bucket integer moments (+ member compaction) */
+  BS_K_INT_RANSAC,  /* per-bucket line hypotheses, inlier counts, arg-max */
   BS_K_IP_KNN,      /* brute-force k nearest neighbours within a point set */
   BS_K_IP_DESC,     /* descriptor gather */
   BS_K_IP_MATCH,    /* best / second descriptor scan (+ slice merge) */
