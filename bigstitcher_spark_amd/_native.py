@@ -217,6 +217,10 @@ def load_lib():
     lib.bs_reset_stats.argtypes = [C.c_void_p]
     lib.bs_debug_last_top5.argtypes = [C.c_void_p, C.c_float * 5,
                                        C.c_int64 * 5]
+    lib.bs_debug_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3]
+    lib.bs_debug_pcm_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3]
+    lib.bs_debug_rowlist.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]
     lib.bs_debug_peak_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64 * 3,
                                        C.c_int, C.c_float * 5, C.c_int64 * 5,
                                        C.POINTER(C.c_int)]
@@ -773,6 +777,31 @@ class Context:
         self._check(self._lib.bs_debug_last_top5(self._h, v, idx),
                     "bs_debug_last_top5")
         return np.array(v[:], np.float32), np.array(idx[:], np.int64)
+
+    def debug_pcm(self, raw=False):
+        """PCM of the last stitched pair as float32 (pz, py, px). Under
+        BS_PCM_MODE=rows the library first rebuilds the whole volume;
+        raw=True returns the buffer as it stands instead (only the rows
+        of debug_rowlist() belong to the pair then)."""
+        fn = self._lib.bs_debug_pcm_raw if raw else self._lib.bs_debug_pcm
+        dims = (C.c_int64 * 3)()
+        self._check(fn(self._h, None, dims), "bs_debug_pcm")
+        px, py, pz = dims[:]
+        out = np.empty((pz, py, px), np.float32)
+        self._check(fn(self._h, out.ctypes.data_as(C.c_void_p), dims),
+                    "bs_debug_pcm")
+        return out
+
+    def debug_rowlist(self):
+        """PCM rows (z * py + y, int32, unordered) the inverse x pass
+        wrote for the last stitched pair under BS_PCM_MODE=rows."""
+        out = np.empty(9 * 512, np.int32)  # 9 * BS_PEAK_ROWS_CAP
+        n = C.c_size_t(0)
+        self._check(
+            self._lib.bs_debug_rowlist(self._h, out.ctypes.data_as(C.c_void_p),
+                                       out.size, C.byref(n)),
+            "bs_debug_rowlist")
+        return out[:n.value].copy()
 
     def debug_peak_scan(self, vol: np.ndarray, mode: str = "auto"):
         """Run the stitch path's peak stage on a (pz, py, px) float32

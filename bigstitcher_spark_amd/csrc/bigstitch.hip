@@ -42,6 +42,7 @@
 #include "rtest_walk.h"
 
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -916,10 +917,19 @@ __device__ __forceinline__ float wave_max_f32(float m) {
  * Z2[k] = A + i*conj(W^k)*B with A = X[k]+conj(X[h-k]),
  * B = X[k]-conj(X[h-k]) (the dropped 1/2 makes the result exactly the
  * UNNORMALIZED length-n inverse, matching the other passes); after the
- * FFT, z[j] = (pcm[2j], pcm[2j+1]) -> vectorized float2 row writes. */
+ * FFT, z[j] = (pcm[2j], pcm[2j+1]) -> vectorized float2 row writes.
+ *
+ * All three inverse x kernels serve three uses through runtime arguments
+ * (DESIGN.md §4 "Sparse PCM"): rows == nullptr walks all nlines lines,
+ * otherwise line i of the walk is rows[i] for i < *nrows_dev (a device
+ * count: no host round trip). store_pcm / store_rowmax switch the two
+ * stores; both branches are wave-uniform and sit around the stores only,
+ * so a row written by a later list pass comes out of the same
+ * instructions as the row whose maximum the first pass took. */
 __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv(
     const f2 *in, float *out, float *rowmax, int n, int log2n, int cx,
-    long cxp, long nlines, const f2 *twg) {
+    long cxp, long nlines, const f2 *twg, const int *rows,
+    const int *nrows_dev, int store_pcm, int store_rowmax) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = n >> 1, log2h = log2n - 1;
   f2 *tw = (f2 *)smem;
@@ -929,11 +939,13 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv(
   for (int i = tid; i < (h >> 1); i += LPB_X * TPL_X) tw[i] = twg[2 * i];
   __syncthreads();
 
-  long ngroups = (nlines + LPB_X - 1) / LPB_X;
+  if (rows) nlines = *nrows_dev;
+  long ngroups = (nlines + LPB_X - 1) / LPB_X; /* block-uniform walk */
   f2 *ld = data + (long)line * h;
   for (long grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     long lid = grp * LPB_X + line;
     bool active = lid < nlines;
+    if (rows) lid = active ? rows[lid] : 0;
     const f2 *src = in + lid * cxp;
     for (int k = tl; k < h; k += TPL_X) {
       f2 v = {0.0f, 0.0f};
@@ -955,11 +967,13 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv(
       float m = -3.0e38f;
       for (int j = tl; j < h; j += TPL_X) {
         f2 z = ld[j];
-        o[j] = z;
+        if (store_pcm) o[j] = z;
         m = fmaxf(m, fmaxf(z.x, z.y));
       }
-      m = wave_max_f32(m); /* TPL_X == 64: the line is one wave */
-      if (tl == 0) rowmax[lid] = m;
+      if (store_rowmax) {
+        m = wave_max_f32(m); /* TPL_X == 64: the line is one wave */
+        if (tl == 0) rowmax[lid] = m;
+      }
     }
     __syncthreads(); /* LDS reused next group */
   }
@@ -1026,7 +1040,8 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_fwd_m(
 
 __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv_m(
     const f2 *in, float *out, float *rowmax, int n, unsigned long long fh,
-    long cxp, long nlines, const f2 *twg) {
+    long cxp, long nlines, const f2 *twg, const int *rows,
+    const int *nrows_dev, int store_pcm, int store_rowmax) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = n >> 1;
   f2 *tw = (f2 *)smem;
@@ -1036,10 +1051,12 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv_m(
   const int tl = tid % TPL_X, line = tid / TPL_X;
   for (int i = tid; i < h; i += LPB_X * TPL_X) tw[i] = twg[2 * i];
   __syncthreads();
-  long ngroups = (nlines + LPB_X - 1) / LPB_X;
+  if (rows) nlines = *nrows_dev;
+  long ngroups = (nlines + LPB_X - 1) / LPB_X; /* block-uniform walk */
   for (long grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     long lid = grp * LPB_X + line;
     bool active = lid < nlines;
+    if (rows) lid = active ? rows[lid] : 0;
     const f2 *src = in + lid * cxp;
     for (int k = tl; k < h; k += TPL_X) {
       f2 v = {0.0f, 0.0f};
@@ -1063,11 +1080,13 @@ __global__ __launch_bounds__(LPB_X *TPL_X) void k_fft_x_inv_m(
       float m = -3.0e38f;
       for (int j = tl; j < h; j += TPL_X) {
         f2 z = ld[(long)j * LPB_X + line];
-        o[j] = z;
+        if (store_pcm) o[j] = z;
         m = fmaxf(m, fmaxf(z.x, z.y));
       }
-      m = wave_max_f32(m);
-      if (tl == 0) rowmax[lid] = m;
+      if (store_rowmax) {
+        m = wave_max_f32(m);
+        if (tl == 0) rowmax[lid] = m;
+      }
     }
     __syncthreads();
   }
@@ -1248,7 +1267,8 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_fwd_w(
 template <int E>
 __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
     const f2 *in, float *out, float *rowmax, long cxp, long nlines,
-    const f2 *twg) {
+    const f2 *twg, const int *rows, const int *nrows_dev, int store_pcm,
+    int store_rowmax) {
   constexpr int h = 64 * E, log2h = 6 + (E == 2) + 2 * (E == 4) + 3 * (E == 8);
   __shared__ f2 tw[h / 2];
   __shared__ f2 twn[h];
@@ -1256,9 +1276,15 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
   for (int i = tid; i < h / 2; i += 64 * XW_WPB) tw[i] = twg[2 * i];
   for (int i = tid; i < h; i += 64 * XW_WPB) twn[i] = twg[i];
   __syncthreads();
-  const int lane = tid & 63, wv = tid >> 6;
-  for (long lid = (long)blockIdx.x * XW_WPB + wv; lid < nlines;
-       lid += (long)gridDim.x * XW_WPB) {
+  const int lane = tid & 63;
+  /* the wave index in a scalar register: the line walk (list lookup
+   * included) then costs no vector registers, which keeps E = 4 within
+   * 128 VGPRs (4 waves/SIMD; `make resource-report`) */
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (rows) nlines = *nrows_dev;
+  for (long li = (long)blockIdx.x * XW_WPB + wv; li < nlines;
+       li += (long)gridDim.x * XW_WPB) {
+    const long lid = rows ? (long)rows[li] : li;
     const f2 *src = in + lid * cxp;
     f2 v[E];
 #pragma unroll
@@ -1273,15 +1299,19 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
       v[e] = {A.x - wb.y, A.y + wb.x}; /* A + i*wb */
     }
     ffth_wave<E>(v, lane, tw, -1);
-    f2 *o = (f2 *)(out + lid * 2 * h);
+    if (store_pcm) {
+      f2 *o = (f2 *)(out + lid * 2 * h);
 #pragma unroll
-    for (int e = 0; e < E; ++e)
-      o[e * 64 + lane] = v[e]; /* (pcm[2p], pcm[2p+1]) */
-    float m = fmaxf(v[0].x, v[0].y);
+      for (int e = 0; e < E; ++e)
+        o[e * 64 + lane] = v[e]; /* (pcm[2p], pcm[2p+1]) */
+    }
+    if (store_rowmax) {
+      float m = fmaxf(v[0].x, v[0].y);
 #pragma unroll
-    for (int e = 1; e < E; ++e) m = fmaxf(m, fmaxf(v[e].x, v[e].y));
-    m = wave_max_f32(m);
-    if (lane == 0) rowmax[lid] = m;
+      for (int e = 1; e < E; ++e) m = fmaxf(m, fmaxf(v[e].x, v[e].y));
+      m = wave_max_f32(m);
+      if (lane == 0) rowmax[lid] = m;
+    }
   }
 }
 
@@ -1597,13 +1627,17 @@ __global__ __launch_bounds__(256) void k_rowmax_ref(const float *pcm, int px,
 
 /* Dominant rows: one thread per row, per-block top five of
  * (rowmax, row) over rows whose maximum beats all 8 neighbour rows.
- * Also clears the row check's |L|, |R| counters (it runs next in stream
- * order), which saves a memset in the launch-latency-bound chain. */
+ * Also clears the row check's |L|, |R| counters and the row list's two
+ * counters rl[0..1] (both kernels run later in stream order), which
+ * saves memsets in the launch-latency-bound chain. */
 __global__ __launch_bounds__(256) void k_peak_rowdom(const float *rowmax,
                                                      int py, int pz,
                                                      bs_peak *wgbuf,
-                                                     int *cnt) {
-  if (blockIdx.x == 0 && threadIdx.x < 2) cnt[threadIdx.x] = 0;
+                                                     int *cnt, int *rl) {
+  if (blockIdx.x == 0 && threadIdx.x < 2) {
+    cnt[threadIdx.x] = 0;
+    rl[threadIdx.x] = 0; /* k_peak_rowlist's count and running |R| */
+  }
   float tv[5];
   long long ti[5];
   for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
@@ -1624,6 +1658,59 @@ __global__ __launch_bounds__(256) void k_peak_rowdom(const float *rowmax,
   pk_block_store(tv, ti, wgbuf);
 }
 
+/* d5 for the whole block: merge k_peak_rowdom's ndom per-block entries
+ * (a few KB from L2; one launch less than a merge kernel in between).
+ * A sentinel (<= -2e38) when fewer than five rows are dominant. Ends in
+ * a barrier, so pk_block_merge may be called again afterwards. */
+__device__ __forceinline__ float pk_dom_d5(const bs_peak *dom, int ndom) {
+  __shared__ float sd5;
+  float tv[5];
+  long long ti[5];
+  for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
+  for (int i = threadIdx.x; i < ndom; i += 256) {
+    const bs_peak p = dom[i];
+    if (p.v > -2.0e38f) pk_insert(tv, ti, p.v, p.idx);
+  }
+  pk_block_merge(tv, ti);
+  if (threadIdx.x == 0) sd5 = tv[4];
+  __syncthreads();
+  return sd5;
+}
+
+/* Row list for the sparse PCM: the rows of R (rowmax >= d5) and their 8
+ * periodic (y,z)-neighbour rows, each once, in rl[2 ..]; rl[0] = their
+ * number, rl[1] = running |R| (both cleared by k_peak_rowdom). These are
+ * all the rows k_peak_rowcheck and the sub-pixel gather read. One thread
+ * per row; a row of R marks itself and its neighbours while the running
+ * |R| is <= cap, so at most 9*cap rows are listed (the list's capacity).
+ * stamp[row] == epoch means "already listed for this pair": the first
+ * marker (atomicExch returns an older epoch) appends the row. stamp is
+ * zeroed when allocated and epoch counts pairs from 1, so it is never
+ * cleared. With d5 the sentinel the list stays empty. With |R| > cap the
+ * list is incomplete and k_peak_rowcheck then reads rows of an earlier
+ * pair: in-bounds memory, and the host discards that result and falls
+ * back (peak_resolve) anyway. */
+__global__ __launch_bounds__(256) void k_peak_rowlist(
+    const float *rowmax, int py, int pz, const bs_peak *dom, int ndom,
+    int cap, int *stamp, int epoch, int *rl) {
+  const float d5 = pk_dom_d5(dom, ndom);
+  if (!(d5 > -2.0e38f)) return; /* block-uniform */
+  const long nrows = (long)py * pz;
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < nrows;
+       r += (long)gridDim.x * 256) {
+    if (!(rowmax[r] >= d5)) continue;
+    if (atomicAdd(&rl[1], 1) >= cap) continue;
+    const int y = (int)(r % py), z = (int)(r / py);
+    for (int dz = -1; dz <= 1; ++dz)
+      for (int dy = -1; dy <= 1; ++dy) {
+        const int yy = (y + dy + py) % py, zz = (z + dz + pz) % pz;
+        const int rr = zz * py + yy;
+        if (atomicExch(&stamp[rr], epoch) != epoch)
+          rl[2 + atomicAdd(&rl[0], 1)] = rr;
+      }
+  }
+}
+
 /* Row check: exhaustive strict-26-maxima test (same comparison as
  * k_peak_generic) of the elements >= d5 in the rows with rowmax >= d5.
  * Every block first merges k_peak_rowdom's ndom per-block lists itself
@@ -1636,19 +1723,10 @@ __global__ __launch_bounds__(256) void k_peak_rowdom(const float *rowmax,
 __global__ __launch_bounds__(256) void k_peak_rowcheck(
     const float *pcm, const float *rowmax, int px, int py, int pz,
     const bs_peak *dom, int ndom, int cap, bs_peak *wgbuf, int *cnt) {
-  __shared__ float sd5;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float d5 = pk_dom_d5(dom, ndom);
   float tv[5];
   long long ti[5];
-  for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
-  for (int i = tid; i < ndom; i += 256) {
-    const bs_peak p = dom[i];
-    if (p.v > -2.0e38f) pk_insert(tv, ti, p.v, p.idx);
-  }
-  pk_block_merge(tv, ti);
-  if (tid == 0) sd5 = tv[4];
-  __syncthreads();
-  const float d5 = sd5;
   for (int k = 0; k < 5; ++k) { tv[k] = -3.0e38f; ti[k] = 0x7fffffffffffffffLL; }
   const long nrows = (long)py * pz;
   int nl = 0;
@@ -2430,6 +2508,14 @@ struct bs_slot {
   bs_peak *dtop5 = nullptr;  /* top five + one entry of counters */
   float *rowmax = nullptr;   /* prefilter: Pz*Py row maxima of pcm */
   size_t rowmax_cap = 0;
+  int *rowstamp = nullptr;   /* sparse PCM: epoch at which a row was listed */
+  size_t rowstamp_cap = 0;
+  int *rowlist = nullptr;    /* [0] count, [1] running |R|, [2..] rows */
+  int row_epoch = 0;         /* pairs whose rows this slot has listed */
+  int pcm_sparse = 0;        /* pcm holds only the listed rows of the pair
+                                whose y-inverted spectrum is in spec[0] */
+  int row_listed = 0;        /* rowlist belongs to the slot's last pair */
+  f2 *twx = nullptr;         /* that pair's x twiddles (full inverse x pass) */
   int pk_prefilter = 0;      /* this pair's top five came from the prefilter */
   bs_cand *dcands = nullptr;
   u64 *dsums = nullptr;
@@ -2481,6 +2567,10 @@ struct bs_ctx {
   size_t dvol_cap = 0;
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   int peak_full = 0; /* BS_PEAK_MODE=full: always the full peak scan */
+  int pcm_rows = 1;  /* BS_PCM_MODE=rows (default): the inverse x pass
+                        writes only the rows the peak stage reads; full =
+                        the whole PCM (forced by BS_PEAK_MODE=full) */
+  bs_slot *dbg_slot = nullptr; /* slot of the last pair (bs_debug_pcm) */
   int corr_wide = 1; /* BS_CORR_MODE=wide (default) | legacy r-test */
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
   bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
@@ -2563,6 +2653,9 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   }
   if (const char *e = getenv("BS_PEAK_MODE")) /* auto (default) | full */
     c->peak_full = strcmp(e, "full") == 0;
+  if (const char *e = getenv("BS_PCM_MODE")) /* rows (default) | full */
+    c->pcm_rows = strcmp(e, "full") != 0;
+  if (c->peak_full) c->pcm_rows = 0; /* the full scan reads every row */
   if (const char *e = getenv("BS_CORR_MODE")) /* wide (default) | legacy */
     c->corr_wide = strcmp(e, "legacy") != 0;
   if (const char *e = getenv("BS_DOG_INIT_CAP")) {
@@ -2632,6 +2725,8 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
              hipSuccess &&
          hipMalloc(&sl.dmerge, 64 * 5 * sizeof(bs_peak)) == hipSuccess &&
          hipMalloc(&sl.dtop5, 6 * sizeof(bs_peak)) == hipSuccess &&
+         hipMalloc(&sl.rowlist, (2 + 9 * BS_PEAK_ROWS_CAP) * sizeof(int)) ==
+             hipSuccess &&
          hipMalloc(&sl.dcands, 64 * sizeof(bs_cand)) == hipSuccess &&
          hipMalloc(&sl.dsums, 64 * 5 * sizeof(u64)) == hipSuccess &&
          hipMalloc(&sl.dpkidx, 8 * sizeof(long long)) == hipSuccess &&
@@ -2674,6 +2769,8 @@ extern "C" void bs_ctx_destroy(bs_ctx *c) {
     (void)hipFree(sl.dmerge);
     (void)hipFree(sl.dtop5);
     (void)hipFree(sl.rowmax);
+    (void)hipFree(sl.rowstamp);
+    (void)hipFree(sl.rowlist);
     (void)hipFree(sl.dcands);
     (void)hipFree(sl.dsums);
     (void)hipFree(sl.dpkidx);
@@ -3008,8 +3105,73 @@ static int peak_ensure(bs_ctx *c, bs_slot *sl) {
   int rc = ensure_dev(c, (void **)&sl->wgpk, &sl->wgpk_cap,
                       (size_t)nwg * 5 * sizeof(bs_peak));
   if (rc) return rc;
-  return ensure_dev(c, (void **)&sl->rowmax, &sl->rowmax_cap,
-                    (size_t)sl->Pz * sl->Py * sizeof(float));
+  rc = ensure_dev(c, (void **)&sl->rowmax, &sl->rowmax_cap,
+                  (size_t)sl->Pz * sl->Py * sizeof(float));
+  if (rc) return rc;
+  /* row stamps (k_peak_rowlist): zeroed once per allocation; the epoch
+   * restarts with them */
+  const size_t old_cap = sl->rowstamp_cap;
+  rc = ensure_dev(c, (void **)&sl->rowstamp, &sl->rowstamp_cap,
+                  (size_t)sl->Pz * sl->Py * sizeof(int));
+  if (rc) return rc;
+  if (sl->rowstamp_cap != old_cap || sl->row_epoch == INT_MAX) {
+    CHK(c, hipMemsetAsync(sl->rowstamp, 0, sl->rowstamp_cap, sl->stream));
+    sl->row_epoch = 0;
+  }
+  return BS_OK;
+}
+
+/* ---- inverse x pass: spec[0] of the slot -> pcm rows and/or rowmax.
+ * ONE kernel per size class serves all three uses (see k_fft_x_inv):
+ *   X_INV_MAX   all rows, row maxima only (pass 1 of the sparse PCM)
+ *   X_INV_LIST  the rows of sl->rowlist, PCM only (pass 2), on a small
+ *               fixed grid that grid-strides over the device-side count
+ *   X_INV_FULL  all rows, both stores (the whole PCM)
+ * Needs sl->Px/Py/Pz/Cx/Cxp, sl->twx and the y-inverted spectrum in
+ * sl->spec. Not timed here: the callers own the bs_tim interval. */
+enum { X_INV_MAX = 0, X_INV_LIST = 1, X_INV_FULL = 2 };
+#define X_INV_LIST_WG 64 /* x 4 lines: 256 rows per sweep */
+
+static void launch_x_inv(bs_slot *sl, int mode) {
+  const int Px = sl->Px;
+  const long Cxp = sl->Cxp, nlines = (long)sl->Pz * sl->Py;
+  const f2 *spec0 = sl->spec;
+  const f2 *twx = sl->twx;
+  const int *rows = mode == X_INV_LIST ? sl->rowlist + 2 : nullptr;
+  const int *nrows_dev = sl->rowlist;
+  const int st_pcm = mode != X_INV_MAX, st_max = mode != X_INV_LIST;
+  const long wgcap = mode == X_INV_LIST ? X_INV_LIST_WG : 4096L;
+  if (!is_pow2(Px)) {
+    long ngrp = (nlines + LPB_X - 1) / LPB_X;
+    size_t lds = ((Px / 2) + 2 * (size_t)LPB_X * (Px / 2)) * sizeof(f2);
+    hipLaunchKernelGGL(k_fft_x_inv_m, dim3(std::min(wgcap, ngrp)),
+                       dim3(LPB_X * TPL_X), lds, sl->stream, spec0, sl->pcm,
+                       sl->rowmax, Px, bs_factorize(Px / 2), Cxp, nlines,
+                       twx, rows, nrows_dev, st_pcm, st_max);
+  } else if (Px >= 128 && Px <= 1024) { /* wave-resident fast path */
+    long ngrp = (nlines + XW_WPB - 1) / XW_WPB;
+    dim3 g(std::min(wgcap, ngrp)), b(64 * XW_WPB);
+    auto xw = [&](auto kern) {
+      hipLaunchKernelGGL(kern, g, b, 0, sl->stream, spec0, sl->pcm,
+                         sl->rowmax, Cxp, nlines, twx, rows, nrows_dev,
+                         st_pcm, st_max);
+    };
+    if (Px == 128)
+      xw(k_fft_x_inv_w<1>);
+    else if (Px == 256)
+      xw(k_fft_x_inv_w<2>);
+    else if (Px == 512)
+      xw(k_fft_x_inv_w<4>);
+    else
+      xw(k_fft_x_inv_w<8>);
+  } else {
+    long ngrp = (nlines + LPB_X - 1) / LPB_X;
+    size_t lds = ((Px / 4) + (size_t)LPB_X * (Px / 2)) * sizeof(f2);
+    hipLaunchKernelGGL(k_fft_x_inv, dim3(std::min(wgcap, ngrp)),
+                       dim3(LPB_X * TPL_X), lds, sl->stream, spec0, sl->pcm,
+                       sl->rowmax, Px, ilog2(Px), sl->Cx, Cxp, nlines, twx,
+                       rows, nrows_dev, st_pcm, st_max);
+  }
 }
 
 /* today's full-volume scan + hierarchical merge -> dtop5[0..4] */
@@ -3041,9 +3203,11 @@ static void peak_launch_full(bs_ctx *c, bs_slot *sl) {
 }
 
 /* prefilter chain: dominant rows -> (d5 +) row check -> dtop5[0..4], with
- * |L| and |R| in the two ints at dtop5[5]. Three small launches, timed
- * as one BS_K_PEAK_ROWS interval. wgpk holds the dominant lists in its
- * first BS_PEAK_ROWS_WG*5 entries and the row check's lists after them. */
+ * |L| and |R| in the two ints at dtop5[5]. Three small launches, or five
+ * when the PCM is sparse (row list + the inverse x pass over it come
+ * before the row check), timed as one BS_K_PEAK_ROWS interval. wgpk
+ * holds the dominant lists in its first BS_PEAK_ROWS_WG*5 entries and
+ * the row check's lists after them. */
 static void peak_launch_rows(bs_ctx *c, bs_slot *sl) {
   const long nrows = (long)sl->Py * sl->Pz;
   int *cnt = (int *)(sl->dtop5 + 5);
@@ -3051,7 +3215,14 @@ static void peak_launch_rows(bs_ctx *c, bs_slot *sl) {
   bs_tim tt(c, BS_K_PEAK_ROWS, sl->stream);
   const int nb = (int)std::min((long)BS_PEAK_ROWS_WG, (nrows + 255) / 256);
   hipLaunchKernelGGL(k_peak_rowdom, dim3(nb), dim3(256), 0, sl->stream,
-                     sl->rowmax, sl->Py, sl->Pz, sl->wgpk, cnt);
+                     sl->rowmax, sl->Py, sl->Pz, sl->wgpk, cnt, sl->rowlist);
+  if (sl->pcm_sparse) {
+    hipLaunchKernelGGL(k_peak_rowlist, dim3(nb), dim3(256), 0, sl->stream,
+                       sl->rowmax, sl->Py, sl->Pz, sl->wgpk, nb * 5,
+                       BS_PEAK_ROWS_CAP, sl->rowstamp, ++sl->row_epoch,
+                       sl->rowlist);
+    launch_x_inv(sl, X_INV_LIST);
+  }
   hipLaunchKernelGGL(k_peak_rowcheck, dim3(nb), dim3(256), 0, sl->stream,
                      sl->pcm, sl->rowmax, sl->Px, sl->Py, sl->Pz, sl->wgpk,
                      nb * 5, BS_PEAK_ROWS_CAP, chk, cnt);
@@ -3086,6 +3257,12 @@ static int peak_resolve(bs_ctx *c, bs_slot *sl, int *fell_back) {
   const int *cnt = (const int *)(sl->htop5 + 5); /* |L|, |R| */
   if (cnt[0] >= 5 && cnt[1] <= BS_PEAK_ROWS_CAP) return BS_OK;
   if (fell_back) *fell_back = 1;
+  if (sl->pcm_sparse) { /* the full scan reads every row: write them all
+                           (spec[0] lives until the slot's next phase A) */
+    bs_tim tt(c, BS_K_FFT_X_INV, sl->stream);
+    launch_x_inv(sl, X_INV_FULL);
+    sl->pcm_sparse = 0;
+  }
   int rc = peak_issue(c, sl, true);
   if (rc) return rc;
   CHK(c, hipEventSynchronize(sl->peaks_ready));
@@ -3306,41 +3483,19 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
     (void)lds;
     launch_y(spec[0], Pz, Py, -1);
   }
+  /* inverse x: with the prefilter on, the normal path takes only the row
+   * maxima here and writes the few rows the peak stage reads after the
+   * row list is known (peak_launch_rows); BS_PCM_MODE=full and
+   * BS_PEAK_MODE=full write the whole PCM */
+  sl->twx = twx;
+  sl->pcm_sparse = c->pcm_rows && !c->peak_full;
+  sl->row_listed = sl->pcm_sparse;
   {
-    long nlines = (long)Pz * Py;
     bs_tim tt(c, BS_K_FFT_X_INV, sl->stream);
-    if (!is_pow2(Px)) {
-      long ngrp = (nlines + LPB_X - 1) / LPB_X;
-      size_t lds = ((Px / 2) + 2 * (size_t)LPB_X * (Px / 2)) * sizeof(f2);
-      hipLaunchKernelGGL(k_fft_x_inv_m, dim3(std::min(4096L, ngrp)),
-                         dim3(LPB_X * TPL_X), lds, sl->stream, spec[0],
-                         sl->pcm, sl->rowmax, Px, bs_factorize(Px / 2), Cxp,
-                         nlines, twx);
-    } else if (Px >= 128 && Px <= 1024) { /* wave-resident fast path */
-      long ngrp = (nlines + XW_WPB - 1) / XW_WPB;
-      dim3 g(std::min(4096L, ngrp)), b(64 * XW_WPB);
-      if (Px == 128)
-        hipLaunchKernelGGL(k_fft_x_inv_w<1>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
-      else if (Px == 256)
-        hipLaunchKernelGGL(k_fft_x_inv_w<2>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
-      else if (Px == 512)
-        hipLaunchKernelGGL(k_fft_x_inv_w<4>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
-      else
-        hipLaunchKernelGGL(k_fft_x_inv_w<8>, g, b, 0, sl->stream, spec[0],
-                           sl->pcm, sl->rowmax, Cxp, nlines, twx);
-    } else {
-      long ngrp = (nlines + LPB_X - 1) / LPB_X;
-      size_t lds = ((Px / 4) + (size_t)LPB_X * (Px / 2)) * sizeof(f2);
-      hipLaunchKernelGGL(k_fft_x_inv, dim3(std::min(4096L, ngrp)),
-                         dim3(LPB_X * TPL_X), lds, sl->stream, spec[0],
-                         sl->pcm, sl->rowmax, Px, ilog2(Px), Cx, Cxp, nlines,
-                         twx);
-    }
+    launch_x_inv(sl, sl->pcm_sparse ? X_INV_MAX : X_INV_FULL);
   }
   c->dbg_pcm = sl->pcm;
+  c->dbg_slot = sl;
   c->dbg_px = Px;
   c->dbg_py = Py;
   c->dbg_pz = Pz;
@@ -3562,9 +3717,12 @@ extern "C" int bs_stitch_batch(bs_ctx *c, const bs_pair_desc *pairs, size_t np,
 
 /* Debug-only: download the PCM of the LAST pair processed by
  * bs_stitch_batch (dims out_dims = {Px, Py, Pz}). Not part of the
- * product surface. */
-extern "C" int bs_debug_pcm(bs_ctx *c, float *out, int64_t out_dims[3]) {
-  if (!c || !out) return BS_EINVAL;
+ * product surface. When that pair's PCM is sparse (BS_PCM_MODE=rows)
+ * the full inverse x pass runs first, from the slot's y-inverted
+ * spectrum, which like the PCM itself is valid until the next batch. */
+static int debug_pcm_copy(bs_ctx *c, float *out, int64_t out_dims[3],
+                          bool rematerialise) {
+  if (!c || !out_dims) return BS_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   CHK(c, hipSetDevice(c->dev));
   out_dims[0] = c->dbg_px;
@@ -3572,8 +3730,51 @@ extern "C" int bs_debug_pcm(bs_ctx *c, float *out, int64_t out_dims[3]) {
   out_dims[2] = c->dbg_pz;
   size_t n = (size_t)c->dbg_px * c->dbg_py * c->dbg_pz;
   if (!n) return BS_EINVAL;
-  if (!c->dbg_pcm) return BS_EINVAL;
+  if (!out) return BS_OK; /* dims query */
+  if (!c->dbg_pcm || !c->dbg_slot) return BS_EINVAL;
+  bs_slot *sl = c->dbg_slot;
+  if (rematerialise && sl->pcm_sparse) {
+    launch_x_inv(sl, X_INV_FULL); /* untimed: not part of any batch */
+    sl->pcm_sparse = 0;
+  }
+  CHK(c, hipStreamSynchronize(sl->stream));
   CHK(c, hipMemcpy(out, c->dbg_pcm, n * 4, hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
+extern "C" int bs_debug_pcm(bs_ctx *c, float *out, int64_t out_dims[3]) {
+  return debug_pcm_copy(c, out, out_dims, true);
+}
+
+/* Debug-only: the LAST pair's PCM buffer as it stands, without
+ * rematerialising: under BS_PCM_MODE=rows only the rows of
+ * bs_debug_rowlist belong to that pair, the rest is whatever earlier
+ * pairs left there. */
+extern "C" int bs_debug_pcm_raw(bs_ctx *c, float *out, int64_t out_dims[3]) {
+  return debug_pcm_copy(c, out, out_dims, false);
+}
+
+/* Debug-only: the LAST pair's row list (k_peak_rowlist: PCM row indices
+ * z*Py + y, unordered), at most `cap` of them into out; *n = their
+ * number. Empty when that pair's PCM was written whole from the start
+ * (BS_PCM_MODE=full, BS_PEAK_MODE=full). */
+extern "C" int bs_debug_rowlist(bs_ctx *c, int32_t *out, size_t cap,
+                                size_t *n) {
+  if (!c || !out || !n) return BS_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  CHK(c, hipSetDevice(c->dev));
+  *n = 0;
+  bs_slot *sl = c->dbg_slot;
+  if (!sl) return BS_EINVAL;
+  if (!sl->row_listed) return BS_OK;
+  CHK(c, hipStreamSynchronize(sl->stream));
+  int cnt = 0;
+  CHK(c, hipMemcpy(&cnt, sl->rowlist, sizeof(int), hipMemcpyDeviceToHost));
+  if (cnt < 0 || cnt > 9 * BS_PEAK_ROWS_CAP) return BS_EINVAL;
+  *n = std::min((size_t)cnt, cap);
+  if (*n)
+    CHK(c, hipMemcpy(out, sl->rowlist + 2, *n * sizeof(int),
+                     hipMemcpyDeviceToHost));
   return BS_OK;
 }
 
@@ -3612,7 +3813,11 @@ extern "C" int bs_debug_peak_scan(bs_ctx *c, const float *pcm_host,
   const size_t n = (size_t)nrows * sl->Px;
   int rc = ensure_dev(c, (void **)&sl->pcm, &sl->pcm_cap, n * sizeof(float));
   if (rc) return rc;
+  /* the uploaded volume is whole: never rebuild rows from a spectrum */
+  sl->pcm_sparse = 0;
+  sl->row_listed = 0;
   c->dbg_pcm = sl->pcm;
+  c->dbg_slot = sl;
   c->dbg_px = sl->Px;
   c->dbg_py = sl->Py;
   c->dbg_pz = sl->Pz;

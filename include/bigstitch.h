@@ -243,10 +243,28 @@ int bs_fuse_volume(bs_ctx *ctx, const bs_fuse_view *views, size_t nviews,
                    void **level_buffers);
 
 /* Debug-only: download the PCM volume of the LAST pair processed by
- * bs_stitch_batch on this ctx (out must hold prod(out_dims) floats after
- * a first call with out=NULL is not supported — query dims via the pair
- * geometry). Not part of the drop-in surface; used by parity tooling. */
+ * bs_stitch_batch on this ctx. out must hold prod(out_dims) floats; a
+ * call with out=NULL only fills out_dims = {Px, Py, Pz}. Not part of the
+ * drop-in surface; used by parity tooling.
+ *
+ * By default (environment variable BS_PCM_MODE=rows, read in
+ * bs_ctx_create; forced to full by BS_PEAK_MODE=full) bs_stitch_batch
+ * writes only the PCM rows its peak stage reads. bs_debug_pcm then first
+ * rebuilds the whole volume from the pair's retained spectrum; it is
+ * valid until the next bs_stitch_batch or bs_debug_peak_scan. */
 int bs_debug_pcm(bs_ctx *ctx, float *out, int64_t out_dims[3]);
+
+/* Debug-only: the same buffer without rebuilding it: under
+ * BS_PCM_MODE=rows only the rows listed by bs_debug_rowlist belong to the
+ * last pair, all other rows hold stale data. */
+int bs_debug_pcm_raw(bs_ctx *ctx, float *out, int64_t out_dims[3]);
+
+/* Debug-only: the PCM rows (index z*Py + y, unordered, no duplicates)
+ * written for the LAST pair under BS_PCM_MODE=rows: the rows whose maximum
+ * reaches the prefilter's threshold and their 8 periodic (y,z)
+ * neighbours. At most cap entries are copied; *n receives their number
+ * (0 when the pair's PCM was written whole). */
+int bs_debug_rowlist(bs_ctx *ctx, int32_t *out, size_t cap, size_t *n);
 
 /* Debug-only: the top five PCM maxima (value, linear index) of the LAST
  * pair processed by bs_stitch_batch, exactly as the candidate stage
