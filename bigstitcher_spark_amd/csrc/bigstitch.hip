@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rtest_walk.h"
+#include "xfft_r4.h"
 
 #include <chrono>
 #include <climits>
@@ -1315,6 +1316,152 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_w(
   }
 }
 
+/* ---- x passes, radix 4 / radix 8 over wave-private LDS (BS_XFFT_MODE=r4;
+ * DESIGN.md §4). Same one-wave-per-row layout and packed-real math as the
+ * _w kernels above, but the h-point FFT is the Stockham schedule of
+ * xfft_r4.h: each lane does whole radix-E butterflies in registers and the
+ * wave exchanges results through its own slice of xb between stages —
+ * natural order in and out, no shuffles, no bit reversal. Same-wave LDS
+ * operations execute in order, so the exchange needs no barrier; the
+ * wavefront-scope fences only keep the compiler from moving a lane's read
+ * of another lane's slot above the write phase. All twiddles depend on
+ * the lane alone and live in registers across the row loop. */
+
+__device__ __forceinline__ void xf_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* h-point FFT of the wave's row: v[r] = z[lane + 64 r] in and out */
+template <int E, int DIR>
+__device__ __forceinline__ void xf_wave_fft(f2 (&v)[E],
+                                            const xf_twset<E, f2> &tws,
+                                            f2 *buf, int lane) {
+  constexpr int NS = xf_geom<E>::NS;
+#pragma unroll
+  for (int si = 0; si < NS; ++si) {
+    xf_stage<E, DIR>(v, tws, si);
+    if (si == NS - 1) break; /* L = 64: already in register order */
+    const int L = xf_L<E>(si);
+    xf_wave_sync(); /* earlier reads of buf are done */
+#pragma unroll
+    for (int s = 0; s < E; ++s) buf[xf_swz<E>(xf_dst<E>(L, lane, s))] = v[s];
+    xf_wave_sync();
+#pragma unroll
+    for (int r = 0; r < E; ++r) v[r] = buf[xf_swz<E>(lane + 64 * r)];
+  }
+}
+
+/* k_fft_x_fwd_w for n = 128*E, E = 4 or 8. One load phase serves full
+ * aligned rows (one dword per packed pair) and partial or odd-aligned
+ * rows (per-element bounds checks); both are in natural order. */
+template <int E>
+__global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_fwd_r4(
+    bs_region in, f2 *out, long cxp, int py, const f2 *twg) {
+  constexpr int h = 64 * E;
+  __shared__ f2 xb[XW_WPB][h]; /* wave-private exchange buffers */
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f2 *buf = xb[wv];
+  xf_twset<E, f2> tws;
+  xf_load_tw<E>(tws, twg, lane, +1);
+  f2 twu[E]; /* unpack twiddles w^k, k = lane + 64 e */
+#pragma unroll
+  for (int e = 0; e < E; ++e) twu[e] = twg[lane + 64 * e];
+  /* my, mz <= 1024 (the FFT size limit): the row walk fits 32 bits, which
+   * keeps the wave-uniform y/z split off the 64-bit division path */
+  const unsigned nlines = (unsigned)in.my * (unsigned)in.mz;
+  for (unsigned lid = blockIdx.x * XW_WPB + wv; lid < nlines;
+       lid += gridDim.x * XW_WPB) {
+    const int z = (int)(lid / (unsigned)in.my);
+    const int y = (int)(lid - (unsigned)z * (unsigned)in.my);
+    const unsigned short *src =
+        in.ptr + (in.oz + z) * in.sxy + (in.oy + y) * in.sx + in.ox;
+    f2 v[E];
+    if (((size_t)src & 3) == 0 && in.mx >= 2 * h) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const unsigned w = ((const unsigned *)src)[lane + 64 * e];
+        v[e] = {(float)(w & 0xFFFF), (float)(w >> 16)};
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int j = lane + 64 * e;
+        v[e] = {2 * j < in.mx ? (float)src[2 * j] : 0.0f,
+                2 * j + 1 < in.mx ? (float)src[2 * j + 1] : 0.0f};
+      }
+    }
+    xf_wave_fft<E, +1>(v, tws, buf, lane);
+    /* Z[h-k] through the buffer: plain layout, mirrored read */
+    xf_wave_sync();
+#pragma unroll
+    for (int e = 0; e < E; ++e) buf[lane + 64 * e] = v[e];
+    xf_wave_sync();
+    f2 *o = out + ((long)z * py + y) * cxp;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int k = lane + 64 * e;
+      const f2 zm = buf[xf_mirror<E>(k)];
+      if (k == 0) {
+        f2 x0, xh;
+        xf_unpack0(v[0], x0, xh);
+        o[0] = x0;
+        o[h] = xh;
+      } else {
+        o[k] = xf_unpack(v[e], zm, twu[e]);
+      }
+    }
+  }
+}
+
+/* k_fft_x_inv_w for n = 128*E, E = 4 or 8: X[k] and X[h-k] are two
+ * coalesced loads (ascending and descending); the row's values come out
+ * of the same instructions whatever the store flags and the row list. */
+template <int E>
+__global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_r4(
+    const f2 *in, float *out, float *rowmax, long cxp, long nlines,
+    const f2 *twg, const int *rows, const int *nrows_dev, int store_pcm,
+    int store_rowmax) {
+  constexpr int h = 64 * E;
+  __shared__ f2 xb[XW_WPB][h];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f2 *buf = xb[wv];
+  xf_twset<E, f2> tws;
+  xf_load_tw<E>(tws, twg, lane, -1);
+  f2 twp[E]; /* pre-process twiddles w^k, k = lane + 64 e */
+#pragma unroll
+  for (int e = 0; e < E; ++e) twp[e] = twg[lane + 64 * e];
+  if (rows) nlines = *nrows_dev;
+  for (long li = (long)blockIdx.x * XW_WPB + wv; li < nlines;
+       li += (long)gridDim.x * XW_WPB) {
+    const long lid = rows ? (long)rows[li] : li;
+    const f2 *src = in + lid * cxp;
+    f2 v[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int k = lane + 64 * e;
+      v[e] = xf_prep(src[k], src[h - k], twp[e]);
+    }
+    xf_wave_fft<E, -1>(v, tws, buf, lane);
+    if (store_pcm) {
+      f2 *o = (f2 *)(out + lid * 2 * h);
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        o[e * 64 + lane] = v[e]; /* (pcm[2p], pcm[2p+1]) */
+    }
+    if (store_rowmax) {
+      float m = fmaxf(v[0].x, v[0].y);
+#pragma unroll
+      for (int e = 1; e < E; ++e) m = fmaxf(m, fmaxf(v[e].x, v[e].y));
+      m = wave_max_f32(m);
+      if (lane == 0) rowmax[lid] = m;
+    }
+  }
+}
+
 /* ------------------------------------------------------------- peak scan */
 
 struct bs_peak {
@@ -2516,6 +2663,7 @@ struct bs_slot {
                                 whose y-inverted spectrum is in spec[0] */
   int row_listed = 0;        /* rowlist belongs to the slot's last pair */
   f2 *twx = nullptr;         /* that pair's x twiddles (full inverse x pass) */
+  int xinv_r4 = 0;           /* that pair's inverse x kernels (BS_XFFT_MODE) */
   int pk_prefilter = 0;      /* this pair's top five came from the prefilter */
   bs_cand *dcands = nullptr;
   u64 *dsums = nullptr;
@@ -2572,6 +2720,10 @@ struct bs_ctx {
                         the whole PCM (forced by BS_PEAK_MODE=full) */
   bs_slot *dbg_slot = nullptr; /* slot of the last pair (bs_debug_pcm) */
   int corr_wide = 1; /* BS_CORR_MODE=wide (default) | legacy r-test */
+  /* BS_XFFT_MODE: x passes at Px = 512 and 1024. r4 (default) = radix-4/8
+   * over wave-private LDS, shfl = the shuffle kernels; r4fwd / r4inv
+   * switch one direction only (A/B runs). Other sizes always use shfl. */
+  int xfft_fwd_r4 = 1, xfft_inv_r4 = 1;
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
   bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
   long dbg_px = 0, dbg_py = 0, dbg_pz = 0;
@@ -2658,6 +2810,10 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   if (c->peak_full) c->pcm_rows = 0; /* the full scan reads every row */
   if (const char *e = getenv("BS_CORR_MODE")) /* wide (default) | legacy */
     c->corr_wide = strcmp(e, "legacy") != 0;
+  if (const char *e = getenv("BS_XFFT_MODE")) { /* r4 (default) | shfl */
+    c->xfft_fwd_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4fwd") == 0;
+    c->xfft_inv_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4inv") == 0;
+  }
   if (const char *e = getenv("BS_DOG_INIT_CAP")) {
     long v = atol(e);
     if (v >= 1) c->dog_init_cap = (size_t)v;
@@ -3161,9 +3317,9 @@ static void launch_x_inv(bs_slot *sl, int mode) {
     else if (Px == 256)
       xw(k_fft_x_inv_w<2>);
     else if (Px == 512)
-      xw(k_fft_x_inv_w<4>);
+      sl->xinv_r4 ? xw(k_fft_x_inv_r4<4>) : xw(k_fft_x_inv_w<4>);
     else
-      xw(k_fft_x_inv_w<8>);
+      sl->xinv_r4 ? xw(k_fft_x_inv_r4<8>) : xw(k_fft_x_inv_w<8>);
   } else {
     long ngrp = (nlines + LPB_X - 1) / LPB_X;
     size_t lds = ((Px / 4) + (size_t)LPB_X * (Px / 2)) * sizeof(f2);
@@ -3377,8 +3533,14 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
       else if (Px == 256)
         hipLaunchKernelGGL(k_fft_x_fwd_w<2>, g, b, 0, sl->stream,
                            sl->reg[t], spec[t], Cxp, Py, twx);
+      else if (Px == 512 && c->xfft_fwd_r4)
+        hipLaunchKernelGGL(k_fft_x_fwd_r4<4>, g, b, 0, sl->stream,
+                           sl->reg[t], spec[t], Cxp, Py, twx);
       else if (Px == 512)
         hipLaunchKernelGGL(k_fft_x_fwd_w<4>, g, b, 0, sl->stream,
+                           sl->reg[t], spec[t], Cxp, Py, twx);
+      else if (c->xfft_fwd_r4)
+        hipLaunchKernelGGL(k_fft_x_fwd_r4<8>, g, b, 0, sl->stream,
                            sl->reg[t], spec[t], Cxp, Py, twx);
       else
         hipLaunchKernelGGL(k_fft_x_fwd_w<8>, g, b, 0, sl->stream,
@@ -3488,6 +3650,7 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
    * row list is known (peak_launch_rows); BS_PCM_MODE=full and
    * BS_PEAK_MODE=full write the whole PCM */
   sl->twx = twx;
+  sl->xinv_r4 = c->xfft_inv_r4;
   sl->pcm_sparse = c->pcm_rows && !c->peak_full;
   sl->row_listed = sl->pcm_sparse;
   {
