@@ -41,6 +41,7 @@
 
 #include "rtest_walk.h"
 #include "xfft_r4.h"
+#include "sfft_r8.h"
 
 #include <chrono>
 #include <climits>
@@ -1462,6 +1463,222 @@ __global__ __launch_bounds__(64 * XW_WPB) void k_fft_x_inv_r4(
   }
 }
 
+/* ---- strided passes at n = 512, radix 8 in registers (BS_SFFT_MODE=r8;
+ * DESIGN.md §4, the schedule and thread mappings of sfft_r8.h). Same tile
+ * and global access shape as k_fft_pass / zf_body — 8 adjacent columns as 4
+ * float4 pairs x 512 elements, a wave instruction moves 16 rows x 64 B —
+ * but the loaded registers ARE stage 0's inputs and the last stage's
+ * outputs ARE the stores, so LDS holds only the two exchanges between the
+ * three stages: no staging, no bit reversal, twiddles in registers. */
+
+/* rows lane + 64 r of a column pair; nl = live lines of the pair (0..2).
+ * A missing line or a row at or past `valid` is zero registers. `full` is
+ * block-uniform: every pair of the chunk has both lines. Then the eight
+ * loads are unconditional and issue back to back: a row at or past `valid`
+ * re-reads row 0 (in range, in cache) and is zeroed by a select, which
+ * keeps the loads free of per-lane branches. Rows are walked by pointer so
+ * that no per-row offset is a loop invariant worth a register pair. */
+__device__ __forceinline__ void sf_load(sf_lines<f2> &v, const f2 *src,
+                                        long base2, long estride, int lane,
+                                        int valid, int nl, bool full) {
+  const f2 *row0 = src + base2;
+  const f2 *p = row0 + lane * estride;
+  if (full) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r, p += 64 * estride) {
+      const bool in = lane + 64 * r < valid;
+      float4 q = *(const float4 *)(in ? p : row0);
+      if (!in) q = {0.0f, 0.0f, 0.0f, 0.0f};
+      sf_split(q, v.a[r], v.b[r]);
+    }
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r, p += 64 * estride) {
+    float4 q = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (lane + 64 * r < valid) {
+      if (nl == 2) {
+        q = *(const float4 *)p;
+      } else if (nl == 1) {
+        const f2 t = *p;
+        q.x = t.x;
+        q.y = t.y;
+      }
+    }
+    sf_split(q, v.a[r], v.b[r]);
+  }
+}
+
+__device__ __forceinline__ void sf_store(const sf_lines<f2> &v, f2 *dst,
+                                         long base2, long estride, int lane,
+                                         int nl, bool full) {
+  f2 *p = dst + base2 + lane * estride;
+#pragma unroll
+  for (int s = 0; s < 8; ++s, p += 64 * estride) {
+    if (full || nl == 2)
+      *(float4 *)p = sf_join<float4>(v.a[s], v.b[s]);
+    else if (nl == 1)
+      *p = v.a[s];
+  }
+}
+
+/* Everything a thread derives from its id inside the tile loop — exchange
+ * base slots, twiddle slots, row pointers — is derived again at each use
+ * from a copy of the id the optimiser cannot see through. Left visible,
+ * they are loop invariants: hoisted, they stay live across the whole chain
+ * (and a stage's twiddles, once in registers, get widened to (w, w) pairs
+ * for the packed multiplies), which costs the kernels a wave of occupancy
+ * or spills. A handful of integer operations per use is the cheaper side. */
+__device__ __forceinline__ int sf_fresh(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+struct sf_ids { /* the thread in both mappings; pair of the owner = wave */
+  int tid, ow;
+  __device__ __forceinline__ int pl() const { return sf_io_pair(sf_fresh(tid)); }
+  __device__ __forceinline__ int il() const { return sf_io_lane(sf_fresh(tid)); }
+  __device__ __forceinline__ int ol() const { return sf_own_lane(sf_fresh(tid)); }
+};
+
+/* exchange: I/O mapping writes (after stage L = 1), block barrier, the
+ * owners read */
+__device__ __forceinline__ void sf_x_io_to_own(sf_lines<f2> &v, float4 *tile,
+                                               const sf_ids &id) {
+  sf_put<float4, 1>(tile, sf_put_base(id.pl(), id.il(), 1), v);
+  __syncthreads();
+  sf_get<float4>(tile, sf_get_base(id.ow, id.ol()), v);
+}
+
+/* exchange: owners write their slice (after stage L = 8), block barrier,
+ * the I/O mapping reads */
+__device__ __forceinline__ void sf_x_own_to_io(sf_lines<f2> &v, float4 *tile,
+                                               const sf_ids &id) {
+  xf_wave_sync(); /* the wave's earlier reads of its slice are done */
+  sf_put<float4, 8>(tile, sf_put_base(id.ow, id.ol(), 8), v);
+  __syncthreads();
+  sf_get<float4>(tile, sf_get_base(id.pl(), id.il()), v);
+}
+
+/* exchange inside the owner's slice (after stage L): no block barrier */
+template <int L>
+__device__ __forceinline__ void sf_x_own(sf_lines<f2> &v, float4 *tile,
+                                         const sf_ids &id) {
+  xf_wave_sync();
+  sf_put<float4, L>(tile, sf_put_base(id.ow, id.ol(), L), v);
+  xf_wave_sync();
+  sf_get<float4>(tile, sf_get_base(id.ow, id.ol()), v);
+}
+
+/* the workgroup's twiddle table (sfft_r8.h) */
+__device__ __forceinline__ void sf_fill_tw(f2 *twt, const f2 *tw2n, int tid) {
+  for (int i = tid; i < SF_TWN; i += SF_THREADS)
+    twt[i] = sf_tw_entry(tw2n, i);
+  __syncthreads();
+}
+
+/* stage si (1 or 2) of butterfly `lane`, twiddles read from the table */
+template <int DIR>
+__device__ __forceinline__ void sf_stage_tw(sf_lines<f2> &v, const f2 *twt,
+                                            int si, int lane) {
+  f2 w[7];
+  sf_get_tw(twt, si, lane, w);
+  sf_stage<DIR>(v, w);
+}
+
+struct sf_tile_pos { /* where the workgroup's chunk and the thread's pair are */
+  long base2; /* element offset of row 0 of the pair */
+  int nl;     /* live lines of the pair, 0..2 */
+  bool full;  /* block-uniform: all four pairs have both lines */
+};
+
+__device__ __forceinline__ sf_tile_pos sf_locate(long wg, int nchunks,
+                                                 long gstride, int nlines,
+                                                 int pl) {
+  const int group = (int)(wg / nchunks);
+  const int x0 = (int)(wg % nchunks) * (2 * SF_PAIRS);
+  const int x2 = x0 + 2 * pl;
+  return {(long)group * gstride + x2, min(max(nlines - x2, 0), 2),
+          x0 + 2 * SF_PAIRS <= nlines};
+}
+
+/* k_fft_pass at n = 512 without the cross-power input, in place.
+ * 3 block barriers and 2 writes + 2 reads of LDS per element and tile. */
+template <int DIR>
+__global__ __launch_bounds__(SF_THREADS)
+__attribute__((amdgpu_waves_per_eu(4))) void k_fft_pass_r8(
+    f2 *data, long estride, long gstride, int nlines, int nchunks,
+    int ngroups, int valid, const f2 *tw2n) {
+  __shared__ float4 tile[SF_TILE];
+  __shared__ f2 twt[SF_TWN];
+  const sf_ids id = {(int)threadIdx.x,
+                     __builtin_amdgcn_readfirstlane(
+                         sf_own_pair((int)threadIdx.x))};
+  sf_fill_tw(twt, tw2n, id.tid);
+  const long nwg = (long)ngroups * nchunks;
+  for (long wg = blockIdx.x; wg < nwg; wg += gridDim.x) {
+    const sf_tile_pos tp = sf_locate(wg, nchunks, gstride, nlines, id.pl());
+    sf_lines<f2> v;
+    sf_load(v, data, tp.base2, estride, id.il(), valid, tp.nl, tp.full);
+    sf_stage0<DIR>(v);
+    sf_x_io_to_own(v, tile, id);
+    sf_stage_tw<DIR>(v, twt, 1, id.ol());
+    sf_x_own_to_io(v, tile, id);
+    sf_stage_tw<DIR>(v, twt, 2, id.il());
+    sf_store(v, data, tp.base2, estride, id.il(), tp.nl, tp.full);
+    __syncthreads(); /* the tile is rewritten by the next chunk */
+  }
+}
+
+/* forward FFT of the I/O-mapped registers; the spectrum ends in the owner
+ * mapping, natural order (v[r] = Z[lane + 64 r] of the wave's pair) */
+__device__ __forceinline__ void sf_fwd_to_owner(sf_lines<f2> &v, float4 *tile,
+                                                const f2 *twt,
+                                                const sf_ids &id) {
+  sf_stage0<+1>(v);
+  sf_x_io_to_own(v, tile, id);
+  sf_stage_tw<+1>(v, twt, 1, id.ol());
+  sf_x_own<8>(v, tile, id);
+  sf_stage_tw<+1>(v, twt, 2, id.ol());
+}
+
+/* zf_body at n = 512: forward z of A and B, cross-power [PIN-EPS], inverse
+ * z, result in place of A. Both spectra meet element-wise in the owner
+ * registers, already in the inverse's input order. 5 block barriers. */
+__global__ __launch_bounds__(SF_THREADS)
+__attribute__((amdgpu_waves_per_eu(3))) void k_fft_z_fused_r8x(
+    f2 *a, const f2 *b, long estride, long gstride, int nlines, int nchunks,
+    int ngroups, int valid_a, int valid_b, float scale, const f2 *tw2n) {
+  __shared__ float4 tile[SF_TILE];
+  __shared__ f2 twt[SF_TWN];
+  const sf_ids id = {(int)threadIdx.x,
+                     __builtin_amdgcn_readfirstlane(
+                         sf_own_pair((int)threadIdx.x))};
+  sf_fill_tw(twt, tw2n, id.tid);
+  const long nwg = (long)ngroups * nchunks;
+  for (long wg = blockIdx.x; wg < nwg; wg += gridDim.x) {
+    const sf_tile_pos tp = sf_locate(wg, nchunks, gstride, nlines, id.pl());
+    sf_lines<f2> va, vb;
+    sf_load(va, a, tp.base2, estride, id.il(), valid_a, tp.nl, tp.full);
+    sf_load(vb, b, tp.base2, estride, id.il(), valid_b, tp.nl, tp.full);
+    sf_fwd_to_owner(va, tile, twt, id); /* B's loads drain under it */
+    __syncthreads(); /* every owner has read A before B's I/O writes */
+    sf_fwd_to_owner(vb, tile, twt, id);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      va.a[r] = sf_crosspower(va.a[r], vb.a[r], scale);
+      va.b[r] = sf_crosspower(va.b[r], vb.b[r], scale);
+    }
+    sf_stage0<-1>(va);
+    sf_x_own<1>(va, tile, id);
+    sf_stage_tw<-1>(va, twt, 1, id.ol());
+    sf_x_own_to_io(va, tile, id);
+    sf_stage_tw<-1>(va, twt, 2, id.il());
+    sf_store(va, a, tp.base2, estride, id.il(), tp.nl, tp.full);
+    __syncthreads(); /* the tile is rewritten by the next chunk */
+  }
+}
+
 /* ------------------------------------------------------------- peak scan */
 
 struct bs_peak {
@@ -2724,6 +2941,12 @@ struct bs_ctx {
    * over wave-private LDS, shfl = the shuffle kernels; r4fwd / r4inv
    * switch one direction only (A/B runs). Other sizes always use shfl. */
   int xfft_fwd_r4 = 1, xfft_inv_r4 = 1;
+  /* BS_SFFT_MODE: strided passes at Py = 512 / Pz = 512. r8 (default) =
+   * radix-8 register stages fused with the I/O (k_fft_pass_r8,
+   * k_fft_z_fused_r8x), lds = the in-LDS radix-2^2 kernels; r8y / r8z
+   * switch the y passes or the fused z chain only (A/B runs). Other sizes,
+   * pad_mode=fast, BS_Y_GLDS, BS_Z_R8 and BS_Z_NT keep their kernels. */
+  int sfft_y_r8 = 1, sfft_z_r8 = 1;
   float *dbg_pcm = nullptr; /* last pair's PCM (points into a slot) */
   bs_peak dbg_top5[5] = {}; /* last pair's top five as phase B used them */
   long dbg_px = 0, dbg_py = 0, dbg_pz = 0;
@@ -2813,6 +3036,10 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   if (const char *e = getenv("BS_XFFT_MODE")) { /* r4 (default) | shfl */
     c->xfft_fwd_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4fwd") == 0;
     c->xfft_inv_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4inv") == 0;
+  }
+  if (const char *e = getenv("BS_SFFT_MODE")) { /* r8 (default) | lds */
+    c->sfft_y_r8 = strcmp(e, "r8") == 0 || strcmp(e, "r8y") == 0;
+    c->sfft_z_r8 = strcmp(e, "r8") == 0 || strcmp(e, "r8z") == 0;
   }
   if (const char *e = getenv("BS_DOG_INIT_CAP")) {
     long v = atol(e);
@@ -3510,7 +3737,11 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
   f2 *twx = is_pow2(Px) ? get_twiddle(c, Px) : get_twiddle_full(c, Px);
   f2 *twy = is_pow2(Py) ? get_twiddle(c, Py) : get_twiddle_full(c, Py);
   f2 *twz = is_pow2(Pz) ? get_twiddle(c, Pz) : get_twiddle_full(c, Pz);
-  if (!twx || !twy || !twz) {
+  /* the radix-8 strided kernels index the half circle of 2 n (xfft_r4.h) */
+  f2 *tws = (Py == SF_N && c->sfft_y_r8) || (Pz == SF_N && c->sfft_z_r8)
+                ? get_twiddle(c, 2 * SF_N)
+                : twy;
+  if (!twx || !twy || !twz || !tws) {
     c->err = "twiddle alloc failed";
     return BS_ENOMEM;
   }
@@ -3566,6 +3797,14 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
                          (const f2 *)nullptr, sp, Py, bs_factorize(Py),
                          Cxp, (long)Py * Cxp, Cx, nchunks, ngroups, valid,
                          dir, 1.0f, twy);
+    } else if (Py == SF_N && c->sfft_y_r8 && !yglds) {
+      dim3 g(std::min(4096L, (long)ngroups * nchunks)), b(SF_THREADS);
+      if (dir > 0)
+        hipLaunchKernelGGL(k_fft_pass_r8<+1>, g, b, 0, sl->stream, sp, Cxp,
+                           (long)Py * Cxp, Cx, nchunks, ngroups, valid, tws);
+      else
+        hipLaunchKernelGGL(k_fft_pass_r8<-1>, g, b, 0, sl->stream, sp, Cxp,
+                           (long)Py * Cxp, Cx, nchunks, ngroups, valid, tws);
     } else if (yglds && Py >= 256) {
       size_t lds2 = ((Py / 2) + 2 * (size_t)LPB_S * Py) * sizeof(f2);
       long nwg = (long)ngroups * nchunks;
@@ -3628,7 +3867,12 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
      * B-register prefetch at 2 blocks/CU) */
     static const bool z_r8 = getenv("BS_Z_R8") != nullptr;
     static const bool z_nt = getenv("BS_Z_NT") != nullptr;
-    if (Pz <= 128)
+    if (Pz == SF_N && c->sfft_z_r8 && !z_r8 && !z_nt)
+      hipLaunchKernelGGL(k_fft_z_fused_r8x, g, dim3(SF_THREADS), 0,
+                         sl->stream, spec[0], (const f2 *)spec[1],
+                         (long)Py * Cxp, Cxp, Cx, nchunks, Py, sl->reg[0].mz,
+                         sl->reg[1].mz, scale, tws);
+    else if (Pz <= 128)
       zf(k_fft_z_fused<1>);
     else if (Pz == 256)
       zf(k_fft_z_fused<2>);
