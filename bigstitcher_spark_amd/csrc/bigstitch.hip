@@ -75,7 +75,16 @@ __device__ __forceinline__ f2 conjmul(f2 a, f2 b) { /* conj(a)*b */
   return {a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
 }
 __device__ __forceinline__ unsigned brev_n(unsigned j, int log2n) {
-  return __brev(j) >> (32 - log2n);
+  /* & 31: a one-point pass (log2n = 0, j = 0) must not shift by 32 */
+  return __brev(j) >> ((32 - log2n) & 31);
+}
+
+/* f2 entries the half twiddle table of an n-point strided pass takes in
+ * LDS: n/2 rounded up to an even count, so that the data region after it
+ * starts 16-byte aligned for its float4 accesses (n = 2: one entry, padded
+ * to two; n = 1: none). */
+__host__ __device__ static inline int tw_lds_n(int n) {
+  return ((n >> 1) + 1) & ~1;
 }
 
 /* In-LDS radix-2^2 DIT FFT over bit-reversed-loaded data. Two radix-2
@@ -337,7 +346,7 @@ __global__ __launch_bounds__(LPB_S *TPL_S) void k_fft_pass(
     float scale, const f2 *twg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f2 *tw = (f2 *)smem;
-  f2 *data = tw + (n >> 1);
+  f2 *data = tw + tw_lds_n(n);
   const int tid = threadIdx.x;
   const int line = tid % LPB_S, tl = tid / LPB_S;
   for (int i = tid; i < (n >> 1); i += LPB_S * TPL_S) tw[i] = twg[i];
@@ -693,7 +702,7 @@ __device__ __forceinline__ void zf_body(
     const f2 *twg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f2 *tw = (f2 *)smem;
-  f2 *da = tw + (n >> 1);
+  f2 *da = tw + tw_lds_n(n);
   const int tid = threadIdx.x;
   const int line = tid % LPB_S, tl = tid / LPB_S;
   for (int i = tid; i < (n >> 1); i += LPB_S * TPL_S) tw[i] = twg[i];
@@ -3447,8 +3456,11 @@ static bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 static f2 *get_twiddle(bs_ctx *c, int n) {
   auto it = c->twiddles.find(n);
   if (it != c->twiddles.end()) return it->second;
-  std::vector<f2> h(n / 2);
-  for (int k = 0; k < n / 2; ++k) {
+  /* n = 1 has no twiddles, but a zero-byte hipMalloc returns a null
+   * pointer with hipSuccess, which the caller reads as a failed
+   * allocation: keep one entry (w^0) */
+  std::vector<f2> h(std::max(n / 2, 1));
+  for (int k = 0; k < (int)h.size(); ++k) {
     double a = -2.0 * M_PI * k / n;
     h[k] = {(float)std::cos(a), (float)std::sin(a)};
   }
@@ -3718,7 +3730,7 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
   int Py = pad1(std::max(sl->m[0][1], sl->m[1][1]));
   int Pz = pad1(std::max(sl->m[0][2], sl->m[1][2]));
   if (Px > 1024 || Py > 1024 || Pz > 1024 || Px < 8) {
-    c->err = "FFT size unsupported (need 8..1024 per axis)";
+    c->err = "FFT size unsupported (need x 8..1024, y and z 1..1024)";
     return BS_EUNSUP;
   }
   int Cx = Px / 2 + 1;
@@ -3822,7 +3834,7 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
                            Py, ilog2(Py), Cxp, (long)Py * Cxp, Cx, nchunks,
                            ngroups, valid, dir, twy);
     } else {
-      size_t lds = ((Py / 2) + (size_t)LPB_S * Py) * sizeof(f2);
+      size_t lds = (tw_lds_n(Py) + (size_t)LPB_S * Py) * sizeof(f2);
       hipLaunchKernelGGL(k_fft_pass,
                          dim3(std::min(4096L, (long)ngroups * nchunks)),
                          dim3(LPB_S * TPL_S), lds, sl->stream, sp,
@@ -3854,7 +3866,7 @@ static int stitch_phaseA(bs_ctx *c, bs_slot *sl, const bs_pair_desc &pd,
   } else { /* fused z chain: fwd z (A,B) + cross-power [PIN-EPS] + inv z
      * in one launch — the z spectra never round-trip through HBM */
     float scale = 1.0f / ((float)Px * (float)Py * (float)Pz);
-    size_t lds = ((Pz / 2) + (size_t)LPB_S * Pz) * sizeof(f2);
+    size_t lds = (tw_lds_n(Pz) + (size_t)LPB_S * Pz) * sizeof(f2);
     bs_tim tt(c, BS_K_FFT_Z_INV, sl->stream);
     dim3 g(std::min(4096L, (long)Py * nchunks)), b(LPB_S * TPL_S);
     auto zf = [&](auto kern) {

@@ -154,6 +154,12 @@ typedef struct {
   int32_t valid; /* 0: no peak passed the overlap test */
 } bs_shift_result;
 
+/* Padded FFT sizes ([PIN-PAD], of the downsampled intervals): x 8..1024,
+ * y and z 1..1024 (pad_mode 1: 8..1024 on every axis, by its rule). A pair
+ * outside that range fails the batch with BS_EUNSUP. A padded size of 1 on
+ * y or z is supported and gives valid = 0, as in the reference restatement:
+ * with periodic wrap a voxel is its own neighbour there, so the PCM has no
+ * strict local maximum. */
 int bs_stitch_batch(bs_ctx *ctx, const bs_pair_desc *pairs, size_t n,
                     const bs_stitch_params *params, bs_shift_result *out);
 
