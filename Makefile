@@ -8,7 +8,7 @@ LIB = bigstitcher_spark_amd/libbigstitch.so
 
 all: $(LIB) cli
 
-$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h bigstitcher_spark_amd/csrc/xfft_r4.h bigstitcher_spark_amd/csrc/sfft_r8.h bigstitcher_spark_amd/csrc/ip_match.h bigstitcher_spark_amd/csrc/bs_ransac.h bigstitcher_spark_amd/csrc/intensity_match.h bigstitcher_spark_amd/csrc/bs_intensity_solve.h include/bigstitch.h
+$(LIB): bigstitcher_spark_amd/csrc/bigstitch.hip bigstitcher_spark_amd/csrc/rtest_walk.h bigstitcher_spark_amd/csrc/rtest_dot.h bigstitcher_spark_amd/csrc/xfft_r4.h bigstitcher_spark_amd/csrc/sfft_r8.h bigstitcher_spark_amd/csrc/ip_match.h bigstitcher_spark_amd/csrc/bs_ransac.h bigstitcher_spark_amd/csrc/intensity_match.h bigstitcher_spark_amd/csrc/bs_intensity_solve.h include/bigstitch.h
 	$(HIPCC) $(CXXFLAGS) -shared -Iinclude $< -o $@
 
 resource-report: bigstitcher_spark_amd/csrc/bigstitch.hip

@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rtest_walk.h"
+#include "rtest_dot.h"
 #include "xfft_r4.h"
 #include "sfft_r8.h"
 
@@ -2395,6 +2396,168 @@ __global__ __launch_bounds__(256) void k_rtest_wide(bs_region a, bs_region b,
   }
 }
 
+/* N rows of one hoisted chunk column: all loads, then all consumes */
+template <int N>
+__device__ __forceinline__ void rd_rows_hoisted(const unsigned short *ap,
+                                                const unsigned short *bp,
+                                                const bs_rd_lane &h,
+                                                long astep, long bstep,
+                                                bs_rd_acc &acc) {
+  bs_rd_step st[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q)
+    st[q] = bs_rd_fetch(ap, bp, h, q * astep, q * bstep);
+#pragma unroll
+  for (int q = 0; q < N; ++q) bs_rd_consume_h(st[q], h, acc);
+}
+
+/* N rows whose 16-byte phase differs from row to row (per-row setup) */
+template <int N>
+__device__ __forceinline__ void rd_rows_perrow(const unsigned short *ap,
+                                               const unsigned short *bp,
+                                               long ea, long eb, long astep,
+                                               long bstep, int nx, int lx,
+                                               int rw, bs_rd_acc &acc,
+                                               uint64_t s[5], int &n) {
+  bs_rw_row rr[N];
+  int nch = 0;
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    rr[q] = bs_rw_setup(ea + q * astep, eb + q * bstep, nx);
+    nch = max(nch, rr[q].nch);
+  }
+  for (int k = lx; k < nch; k += rw) {
+    if (n > BS_RD_MAX_CHUNKS - N) {
+      bs_rd_widen(acc, s);
+      n = 0;
+    }
+    n += N;
+    bs_rw_step st[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) st[q] = bs_rw_fetch(ap, bp, rr[q], k);
+#pragma unroll
+    for (int q = 0; q < N; ++q) bs_rd_consume(st[q], rr[q].de, acc);
+  }
+}
+
+#define BS_RD_MAX_CANDS 64 /* = the slot buffers' capacity (dcands, dsums) */
+
+/* The same scan and the same loads as k_rtest_wide (BS_CORR_MODE=dot, the
+ * default), with
+ *  - the chunk sums from 8-bit dot products into thirteen u32 accumulators
+ *    (rtest_dot.h), widened to the five u64 once per (block, candidate);
+ *  - masks, realign phase and B chunk choice hoisted out of the row loop
+ *    when both row strides are multiples of 8 elements (chunk index outer,
+ *    rows inner); the per-row derivation stays for other strides;
+ *  - a thread's last 1..ROWS-1 rows issued together as well;
+ *  - no block barrier inside the candidate loop: each wave adds its reduced
+ *    sums into LDS slots of its own, the four waves run through the list
+ *    independently, and after ONE barrier the slots are summed and one
+ *    global add goes out per live (candidate, sum).
+ *
+ * Overflow (see rtest_dot.h): a lane may add BS_RD_MAX_CHUNKS = 4128 chunks
+ * between two widenings. With regions of at most 1024 per axis a lane
+ * reaches, per (block, candidate): rows per thread <= ceil(1024 / (gy *
+ * rpg)) with rpg = 256 / rw rows per block step, times ceil(nch / rw)
+ * chunks per row. Rows of up to 64 chunks have one chunk per lane and row,
+ * at most 1024 * 64 / 256 = 256 chunks at gy = 1; longer rows (rw = 64,
+ * rpg = 4, nch <= (1024 + 14) / 8 = 129 -> 3 chunks) at most 256 * 3 = 768.
+ * Every gy >= 1 stays under the bound by a factor of five; the lane's chunk
+ * counter n still widens early, so nothing depends on those limits. */
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(4))) void k_rtest_dot(
+    bs_region a, bs_region b, const bs_cand *cands, int nc, u64 *sums) {
+  constexpr int ROWS = 3;
+  static_assert(ROWS == 3, "the tail below issues 2 rows, then 1");
+  __shared__ u64 slot[4][BS_RD_MAX_CANDS * 5];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int z = blockIdx.x;
+  u64 *ws = slot[wave];
+  /* a wave's slots are touched by that wave alone until the barrier */
+  for (int i = lane; i < nc * 5; i += 64) ws[i] = 0;
+  const bool hoist = bs_rd_can_hoist(a.sx, b.sx);
+  for (int ci = 0; ci < nc; ++ci) {
+    const bs_cand c = cands[ci];
+    if (z < c.loz || z >= c.loz + c.nz) continue; /* block-uniform */
+    const int nchmax = bs_rw_max_chunks(c.nx);
+    int rw = 1;
+    while (rw < nchmax && rw < 64) rw <<= 1;
+    const int rsh = __ffs(rw) - 1;
+    const int rpg = 256 >> rsh;
+    const int lx = tid & (rw - 1);
+    const int lr = tid >> rsh;
+    const int rstride = gridDim.y * rpg;
+    const int r0 = blockIdx.y * rpg + lr;
+    const long ea0 =
+        (a.oz + z) * a.sxy + (a.oy + c.loy + r0) * a.sx + a.ox + c.lox;
+    const long eb0 = (b.oz + z + c.sz) * b.sxy +
+                     (b.oy + c.loy + c.sy + r0) * b.sx + b.ox + c.lox + c.sx;
+    const long astep = (long)rstride * a.sx, bstep = (long)rstride * b.sx;
+    uint64_t s[5] = {0, 0, 0, 0, 0};
+    bs_rd_acc acc;
+    bs_rd_zero(acc);
+    int n = 0; /* chunks in acc since the last widen */
+    if (hoist) {
+      const bs_rw_row row0 = bs_rw_setup(ea0, eb0, c.nx);
+      for (int k = lx; k < row0.nch; k += rw) {
+        const bs_rd_lane h = bs_rd_hoist(row0, k);
+        const unsigned short *ap = a.ptr, *bp = b.ptr;
+        int r = r0;
+        for (; r + (ROWS - 1) * rstride < c.ny; r += ROWS * rstride) {
+          if (n > BS_RD_MAX_CHUNKS - ROWS) {
+            bs_rd_widen(acc, s);
+            n = 0;
+          }
+          n += ROWS;
+          rd_rows_hoisted<ROWS>(ap, bp, h, astep, bstep, acc);
+          ap += ROWS * astep;
+          bp += ROWS * bstep;
+        }
+        if (n > BS_RD_MAX_CHUNKS - ROWS) {
+          bs_rd_widen(acc, s);
+          n = 0;
+        }
+        if (r + rstride < c.ny) {
+          n += 2;
+          rd_rows_hoisted<2>(ap, bp, h, astep, bstep, acc);
+        } else if (r < c.ny) {
+          n += 1;
+          rd_rows_hoisted<1>(ap, bp, h, astep, bstep, acc);
+        }
+      }
+    } else {
+      int r = r0;
+      long ea = ea0, eb = eb0;
+      for (; r + (ROWS - 1) * rstride < c.ny; r += ROWS * rstride) {
+        rd_rows_perrow<ROWS>(a.ptr, b.ptr, ea, eb, astep, bstep, c.nx, lx,
+                             rw, acc, s, n);
+        ea += ROWS * astep;
+        eb += ROWS * bstep;
+      }
+      if (r + rstride < c.ny)
+        rd_rows_perrow<2>(a.ptr, b.ptr, ea, eb, astep, bstep, c.nx, lx, rw,
+                          acc, s, n);
+      else if (r < c.ny)
+        rd_rows_perrow<1>(a.ptr, b.ptr, ea, eb, astep, bstep, c.nx, lx, rw,
+                          acc, s, n);
+    }
+    bs_rd_widen(acc, s);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const u64 p = wave_sum_u64(s[q]);
+      if (lane == 0) ws[ci * 5 + q] += p;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nc * 5; i += 256) {
+    const int ci = i / 5;
+    const int loz = cands[ci].loz, nz = cands[ci].nz;
+    if (z < loz || z >= loz + nz) continue; /* skipped: nothing to add */
+    atomicAdd(&sums[i], slot[0][i] + slot[1][i] + slot[2][i] + slot[3][i]);
+  }
+}
+
 /* ---------------------------------------------------------------- fusion */
 
 struct bs_dev_view {
@@ -2945,7 +3108,7 @@ struct bs_ctx {
                         writes only the rows the peak stage reads; full =
                         the whole PCM (forced by BS_PEAK_MODE=full) */
   bs_slot *dbg_slot = nullptr; /* slot of the last pair (bs_debug_pcm) */
-  int corr_wide = 1; /* BS_CORR_MODE=wide (default) | legacy r-test */
+  int corr_mode = 2; /* BS_CORR_MODE: 0 legacy | 1 wide | 2 dot (default) */
   /* BS_XFFT_MODE: x passes at Px = 512 and 1024. r4 (default) = radix-4/8
    * over wave-private LDS, shfl = the shuffle kernels; r4fwd / r4inv
    * switch one direction only (A/B runs). Other sizes always use shfl. */
@@ -3040,8 +3203,10 @@ extern "C" int bs_ctx_create(bs_ctx **out, int device_id) {
   if (const char *e = getenv("BS_PCM_MODE")) /* rows (default) | full */
     c->pcm_rows = strcmp(e, "full") != 0;
   if (c->peak_full) c->pcm_rows = 0; /* the full scan reads every row */
-  if (const char *e = getenv("BS_CORR_MODE")) /* wide (default) | legacy */
-    c->corr_wide = strcmp(e, "legacy") != 0;
+  if (const char *e = getenv("BS_CORR_MODE")) { /* dot (default) | wide | legacy */
+    if (strcmp(e, "legacy") == 0) c->corr_mode = 0;
+    else if (strcmp(e, "wide") == 0) c->corr_mode = 1;
+  }
   if (const char *e = getenv("BS_XFFT_MODE")) { /* r4 (default) | shfl */
     c->xfft_fwd_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4fwd") == 0;
     c->xfft_inv_r4 = strcmp(e, "r4") == 0 || strcmp(e, "r4inv") == 0;
@@ -3952,6 +4117,10 @@ static int rtest_issue(bs_ctx *c, bs_slot *sl) {
                    [](const bs_hostcand &x, const bs_hostcand &y) {
                      return x.gc.sz < y.gc.sz;
                    });
+  if (sl->hc.size() > BS_RD_MAX_CANDS) { /* dcands, dsums, LDS slots */
+    c->err = "r-test: more than 64 candidates";
+    return BS_EINVAL;
+  }
   std::vector<bs_cand> gc(sl->hc.size());
   for (size_t i = 0; i < sl->hc.size(); ++i) gc[i] = sl->hc[i].gc;
   CHK(c, hipMemcpyAsync(sl->dcands, gc.data(), gc.size() * sizeof(bs_cand),
@@ -3968,7 +4137,9 @@ static int rtest_issue(bs_ctx *c, bs_slot *sl) {
       const char *e = getenv("BS_CORR_GY");
       return e ? atoi(e) : 8; /* measured: 8 > 4 > 2 >> 1 at 512^3 */
     }();
-    hipLaunchKernelGGL(c->corr_wide ? k_rtest_wide : k_rtest,
+    hipLaunchKernelGGL(c->corr_mode == 2   ? k_rtest_dot
+                       : c->corr_mode == 1 ? k_rtest_wide
+                                           : k_rtest,
                        dim3((unsigned)maxz, corr_gy), dim3(256),
                        0, sl->stream, sl->reg[0], sl->reg[1], sl->dcands,
                        (int)gc.size(), sl->dsums);

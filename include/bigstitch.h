@@ -297,7 +297,7 @@ int bs_debug_peak_scan(bs_ctx *ctx, const float *pcm_host,
  * BS_K_CORR. sums_out[i] = {sum a, sum b, sum aa, sum bb, sum ab} over
  * the overlap of shift i and nvox_out[i] its voxel count (all zero when
  * the overlap is empty). Which kernel runs is fixed per context by the
- * environment variable BS_CORR_MODE (wide | legacy) read in
+ * environment variable BS_CORR_MODE (dot | wide | legacy) read in
  * bs_ctx_create. */
 int bs_debug_rtest(bs_ctx *ctx, const bs_pair_desc *pair,
                    const int32_t (*shifts)[3], int n,

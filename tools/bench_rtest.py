@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Solo timing of the production r-test (k_rtest / k_rtest_wide, chosen by
-BS_CORR_MODE) through bs_debug_rtest: the launch phase B makes, alone on
+"""Solo timing of the production r-test (k_rtest / k_rtest_wide /
+k_rtest_dot, chosen by BS_CORR_MODE = legacy | wide | dot) through bs_debug_rtest: the launch phase B makes, alone on
 the device, HIP-event timed (stat `corr`).
 
 Geometry is the headline benchmark's: two 512^3 uint16 synthetic views and
@@ -15,7 +15,7 @@ filter). Run once per x-shift parity, boxes otherwise alike:
 Prints one JSON line: median / min / max ms of --launches launches, the
 scanned bytes (4 per voxel pair, candidates summed; shared planes hit L2
 so HBM bytes are lower) and the rate they imply. Records:
-profiles/rtest_wide_solo.json."""
+profiles/rtest_wide_solo.json, profiles/rtest_dot_solo.json."""
 
 import argparse
 import json

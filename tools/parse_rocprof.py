@@ -44,6 +44,7 @@ NAME_MAP = {
     "k_peak_tile": ["peak"],
     "k_rtest": ["corr"],
     "k_rtest_wide": ["corr"],  # BS_CORR_MODE=wide (16 B/lane -> x1)
+    "k_rtest_dot": ["corr"],  # BS_CORR_MODE=dot (same loads as wide)
     "k_fuse": ["fuse"],
 }
 
